@@ -5,7 +5,14 @@ Workload: exact top-100 of batch-64 queries over a 10M x 768 synthetic corpus (u
 cosine == inner product), the configuration BASELINE.json's metric is quoted on.  One "step" is one
 batch of 64 queries answered end to end (query prep, scan, select, exact re-score, merge).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run builds the corpus, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, `dtype`,
+the timed region's own search statistics).  --dump-outputs DIR then also writes the last timed step's results, as a
+caller of the search receives them, to DIR/topk_scores.npy (float32 [batch, k]) and DIR/topk_ids.npy (the int64 global
+row ids as float64, exact below 2^53); the corpus and the queries come from fixed seeds, so two builds run with the same
+arguments can be compared output for output.  Everything else below (`roofline`, `recall_at_k`,
+`same_results_from_the_f16_image`, `facade`, `legs`, `cpu_baseline`) is measured only with --full.
 
 N = 1: the whole corpus sits on one MI355X (fp32 rows + blocked f16 image + its 12-bit image = 57.6 GB).
 N > 1 (launched by torch.distributed.run, one rank per GPU): the corpus is row-sharded, every rank
@@ -56,6 +63,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's top-k scores and ids to DIR/topk_scores.npy and DIR/topk_ids.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the scan kernel's own time and "
+                         "roofline, the f16-image cross-check, the facade leg, the other configurations' legs, recall@k "
+                         "against the oracle and the CPU baseline (the --no-* options below switch parts of it off)")
     ap.add_argument("--rows", type=int, default=10_000_000, help="total corpus rows (all ranks)")
     ap.add_argument("--dim", type=int, default=768)
     ap.add_argument("--batch", type=int, default=64)
@@ -82,7 +95,10 @@ def parse():
     ap.add_argument("--one-device", action="store_true", help="rehearsal: every rank uses cuda:0")
     ap.add_argument("--force-dist", action="store_true",
                     help="rehearsal on one GPU: run the N > 1 pipeline (process group, all-gather, merge) with world size 1")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def gen_shard(rows, dim, shard, device, chunk=262_144, centroids=0, sigma=0.0):
@@ -576,10 +592,12 @@ def main():
     gc.disable()
 
     nb = args.steps + args.warmup
-    n_serial = max(0, args.serial_launches)
+    # (Q keeps room for the serialised batches in a plain run too: the same shape draws the same queries)
+    n_q_serial = max(0, args.serial_launches)
+    n_serial = n_q_serial if args.full else 0
     gq = torch.Generator(device=dev)
     gq.manual_seed(4321)
-    Q = torch.randn((nb + n_serial, args.batch, args.dim), generator=gq, device=dev, dtype=torch.float32)
+    Q = torch.randn((nb + n_q_serial, args.batch, args.dim), generator=gq, device=dev, dtype=torch.float32)
     # steps are issued asynchronously and overlap (the small kernels of neighbouring batches run beside the scan).
     # N = 1: three rotating sets of output buffers and streams.
     # N > 1: anorag_hip.sharded.ShardedStream — the shard's search of a batch is launched and left in flight; the partial
@@ -653,6 +671,71 @@ def main():
     st_all = idx.last_stats()
     scan_bytes = st_all["scan_bytes"]
     n_fallback, n_cand = st_all["n_fallback"], st_all["n_candidates"]
+    if dist_on:
+        t = torch.tensor([dt], device=dev if args.backend == "nccl" else "cpu", dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, Dres, Ires)
+    if args.full:
+        full_run(args, idx, dev, Q, Dl, Il, streams, Dres, Ires, dt, scan_bytes, n_fallback, n_cand, nb, n_serial, per,
+                 rows_total, my_rows, row0, world, rank, dist, dist_on, G)
+    elif rank == 0:
+        print(json.dumps(headline(args, dt, scan_bytes / max(1, args.steps), n_fallback, n_cand, per, rows_total, world,
+                                  dist_on, G)), flush=True)
+    idx.close()
+    if dist_on:
+        dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, Dres, Ires):
+    """the last timed step's top-k as a caller receives it: scores float32 [batch, k], global row ids (int64, -1 = none)
+    as float64 — exact for every id below 2^53"""
+    os.makedirs(out_dir, exist_ok=True)
+    D = torch.as_tensor(Dres).cpu().numpy().astype(np.float32, copy=False)
+    ids = torch.as_tensor(Ires).cpu().numpy()
+    np.save(os.path.join(out_dir, "topk_scores.npy"), D)
+    np.save(os.path.join(out_dir, "topk_ids.npy"), ids.astype(np.float64))
+
+
+def headline(args, dt, bytes_per_step, n_fallback, n_cand, per, rows_total, world, dist_on, G):
+    """the fields of the result line that a plain run measures (the timed region and the library's statistics of it)"""
+    bytes_per_value = bytes_per_step / max(1.0, float(-(-per // 32) * 32) * args.dim)
+    twelve = bytes_per_value < 1.75
+    return {
+        "metric": "queries/sec + recall@k vs CPU ref, 10M×768 corpus, batch-64 top-100",
+        "value": args.batch * args.steps / dt,
+        "unit": "queries/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": ("f16 scan (MFMA f16 x f16, f32 accumulate; the scanned image keeps the top 12 bits of every stored f16 — "
+                  "ANR_OPT_SCAN_BITS) + f32 rows re-scored in f64" if twelve else
+                  "f16 scan (MFMA, f32 accumulate) + f32 rows re-scored in f64"),
+        "data": "synthetic",
+        "config": {
+            "workload": f"{rows_total} x {args.dim} unit-norm Gaussian corpus, batch-{args.batch} top-{args.k} "
+                        f"exact cosine search",
+            "rows_total": rows_total,
+            "rows_per_gpu": per,
+            "dim": args.dim,
+            "batch": args.batch,
+            "k": args.k,
+            "parallelism": (f"row-shard x{world}, partial top-k of {G} batches per RCCL all-gather" if dist_on
+                            else "single GPU"),
+        },
+        "exact_fallback_queries": n_fallback,
+        "candidates_per_query": n_cand / max(1, args.steps * args.batch),
+    }
+
+
+def full_run(args, idx, dev, Q, Dl, Il, streams, Dres, Ires, dt, scan_bytes, n_fallback, n_cand, nb, n_serial, per,
+             rows_total, my_rows, row0, world, rank, dist, dist_on, G):
+    """--full: everything after the timed region that the headline figure does not need; prints the full result line"""
     # what the device did inside the timed region, from the library's batch log (device clock stamps left by the kernels
     # themselves; no timing events sit in the batches' queues): the main scans' own spans and the scan-to-scan period
     rec, _ = idx.batch_log(min(args.steps, 512), correlate=False)
@@ -664,10 +747,6 @@ def main():
                 "scan_to_scan_ms_max": float(np.max(np.diff(first))) / 1e6, "batches_logged": int(rec.shape[0]),
                 "note": "first workgroup start -> last workgroup end of each main scan (spans of neighbouring scans overlap: "
                         "the next scan's workgroups take over CU by CU), and start-to-start periods, device clock"}
-    if dist_on:
-        t = torch.tensor([dt], device=dev if args.backend == "nccl" else "cpu", dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt = float(t.item())
     # the scan kernel's own duration (rank 0's shard): serialised batches, outside the timed region
     Dk, Ik = Dl[0].clone(), Il[0].clone()  # scratch outputs: the last timed batch's results stay untouched
     ker_ms, ker_bytes = (serial_kernel_time(idx, Q, nb, n_serial, args.batch, args.k, Dk.data_ptr(), Ik.data_ptr(),
@@ -746,7 +825,6 @@ def main():
         tnotes = []
         _bpl = ker_bytes if ker_ms else scan_bytes / max(1, args.steps)
         traffic = pmc_traffic(per, args.dim, tnotes, _bpl / max(1.0, float(-(-per // 32) * 32) * args.dim))
-        qps = args.batch * args.steps / dt
         ms_step = dt / args.steps * 1e3
         if ker_ms:
             achieved = (ker_bytes / 1e9) / (ker_ms / 1e3)
@@ -759,38 +837,11 @@ def main():
             print(f"bench.py: kernel time per launch {ms_launch:.4f} ms exceeds the step time {ms_step:.4f} ms", file=sys.stderr)
         bpl = ker_bytes if ker_ms else scan_bytes / max(1, args.steps)
         bytes_per_value = bpl / max(1.0, float(-(-per // 32) * 32) * args.dim)
-        twelve = bytes_per_value < 1.75
-        out = {
-            "metric": "queries/sec + recall@k vs CPU ref, 10M×768 corpus, batch-64 top-100",
-            "value": qps,
-            "unit": "queries/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": ("f16 scan (MFMA f16 x f16, f32 accumulate; the scanned image keeps the top 12 bits of every stored f16 — "
-                      "ANR_OPT_SCAN_BITS) + f32 rows re-scored in f64" if twelve else
-                      "f16 scan (MFMA, f32 accumulate) + f32 rows re-scored in f64"),
-            "data": "synthetic",
-            "config": {
-                "workload": f"{rows_total} x {args.dim} unit-norm Gaussian corpus, batch-{args.batch} top-{args.k} "
-                            f"exact cosine search",
-                "rows_total": rows_total,
-                "rows_per_gpu": per,
-                "dim": args.dim,
-                "batch": args.batch,
-                "k": args.k,
-                "parallelism": (f"row-shard x{world}, partial top-k of {G} batches per RCCL all-gather" if dist_on
-                                else "single GPU"),
-            },
+        out = headline(args, dt, bpl, n_fallback, n_cand, per, rows_total, world, dist_on, G)
+        out.update({
             "recall_at_k": recall,
             "recall_queries": (args.batch if args.recall_queries < 0 else args.recall_queries),
             "same_results_from_the_f16_image": same_as_f16,
-            "exact_fallback_queries": n_fallback,
-            "candidates_per_query": n_cand / max(1, args.steps * args.batch),
             "roofline": {
                 "bound": "hbm",
                 "kernel": "k_scan",
@@ -810,7 +861,7 @@ def main():
                 "launch_le_step": consistent,
                 "frac_end_to_end": (scan_bytes / max(1, args.steps) / 1e9) / (ms_step / 1e3) / HBM_PEAK_GBPS,
             },
-        }
+        })
         if legs is not None:
             out["legs"] = legs
         if facade is not None:
@@ -818,9 +869,6 @@ def main():
         if not args.no_cpu and world == 1:
             out["cpu_baseline"] = cpu_baseline(args, world)
         print(json.dumps(out), flush=True)
-    idx.close()
-    if dist_on:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -16,15 +16,15 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 if [[ $STEPS == *1* ]]; then
 echo "[1] bench" >&2
-python3 $R/bench.py > $O/${ROUND}_bench_1gpu.json 2> $O/bench.err
+python3 $R/bench.py --full > $O/${ROUND}_bench_1gpu.json 2> $O/bench.err
 # (the profiled run leaves out the extra legs, the CPU legs and the facade leg: every k_scan<false,...> launch in the stats is a
 # 10 M-row launch of the headline workload, so the kernel's average there is comparable with roofline.ms_per_launch)
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kstats -- python3 $R/bench.py --no-cpu --recall-queries 0 --no-facade --no-legs > $O/bench_prof.json 2> $O/bench_prof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kstats -- python3 $R/bench.py --full --no-cpu --recall-queries 0 --no-facade --no-legs > $O/bench_prof.json 2> $O/bench_prof.err
 cp $(ls $O/kstats/*/*kernel_stats.csv | head -1) $O/${ROUND}_bench_10m_1gpu_kernel_stats.csv
 rm -rf $O/kstats
 # the same command with ONE batch in flight: scans never overlap, so rocprofv3's average k_scan<false,...> duration IS the kernel's
 # time (with three in flight the next scan's workgroups take over CU by CU and the profiler's span of a scan includes that wait)
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kstats1 -- python3 $R/bench.py --in-flight 1 --no-cpu --recall-queries 0 --no-facade --no-legs > $O/bench_prof_serial.json 2> $O/bench_prof_serial.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kstats1 -- python3 $R/bench.py --full --in-flight 1 --no-cpu --recall-queries 0 --no-facade --no-legs > $O/bench_prof_serial.json 2> $O/bench_prof_serial.err
 cp $(ls $O/kstats1/*/*kernel_stats.csv | head -1) $O/${ROUND}_bench_10m_1gpu_in_flight_1_kernel_stats.csv
 rm -rf $O/kstats1
 fi
