@@ -68,7 +68,8 @@ struct Workspace {
   std::vector<int> rec_lists, rec_scan, rec_dense;
   int64_t seq = 0;
   bool shadow = false;             // the batch's side kernels were the shadow-sized ones
-  bool f12 = false;                // the batch's streaming pass read the 12-bit image
+  bool f12 = false;                // the batch's streaming pass read a coarse image (12 or 8 bits)
+  int bits = 16;                   // ... which one
   int f12_level = 0;               // ... at this level of the K' ladder
   hipEvent_t ev_in = nullptr, ev_done = nullptr, ev_t0 = nullptr, ev_t1 = nullptr;
   hipEvent_t ev_pre = nullptr, ev_scan = nullptr;  // role streams: ladder ready (pre -> main), scan done (main -> post)
@@ -91,14 +92,16 @@ struct anr_index {
   float *x32 = nullptr;
   _Float16 *x16 = nullptr;
   float *rowbias = nullptr;
-  unsigned *xstat = nullptr;  // [4]: max ||x||, max ||x16 - x||, f16-range flag, max ||x12 - x||
+  unsigned *xstat = nullptr;  // [5]: max ||x||, max ||x16 - x||, f16-range flag, max ||x12 - x||, max ||x8 - x||
   unsigned *x12 = nullptr;    // the 12-bit image the streaming scan reads when scan_bits == 12 (index_kernels.hpp)
   unsigned *xstat12 = nullptr;  // [2]: max ||x||, max(||x16 - x||, ||x12 - x||) — the certificate's statistics of such batches
-  int scan_bits = 0;          // ANR_OPT_SCAN_BITS: 0 auto, 12, 16
-  bool f12_suspended = false; // the corpus proved too dense for the 12-bit image (adapt_overfetch): batches read x16 again
+  unsigned char *x8 = nullptr;  // the 8-bit image the streaming scan reads when scan_bits == 8
+  unsigned *xstat8 = nullptr;   // [2]: max ||x||, max(||x16 - x||, ||x8 - x||)
+  int scan_bits = 0;          // ANR_OPT_SCAN_BITS: 0 auto, 8, 12, 16
+  bool f12_suspended = false; // the corpus proved too dense for the coarse image (adapt_overfetch): batches read x16 again
   int f12_strikes = 0;
-  bool x12_no_memory = false; // the 12-bit image could not be allocated: not tried again until rows are added or the option is set
-  // K' of the 12-bit batches: its own ladder of quarter steps (kF12Steps) and a step-down that backs off
+  bool x12_no_memory = false; // the coarse image could not be allocated: not tried again until rows are added or the option is set
+  // K' of the coarse-image batches: its own ladder of quarter steps (kF12Steps) and a step-down that backs off
   int f12_level = 0, f12_clean = 0, f12_hold = 64, f12_lowered = 0;
   hipStream_t stream = nullptr;                        // adds, exact path, copies
   hipStream_t bstream[kWorkspaces] = {nullptr, nullptr, nullptr};  // one per in-flight batch
@@ -188,10 +191,14 @@ int grow_storage(anr_index *h, int64_t need_rows) {
   float *nx32 = nullptr;
   _Float16 *nx16 = nullptr;
   unsigned *nx12 = nullptr;
+  unsigned char *nx8 = nullptr;
   float *nbias = nullptr;
   int rc = dev_alloc(&nx32, ncap * h->dim, false);
   if (rc == ANR_OK) rc = dev_alloc(&nx16, ncap * h->dimp, true);
-  if (rc == ANR_OK && (h->scan_bits == 12 || h->x12)) rc = dev_alloc(&nx12, ncap * h->dimp * 3 / 8, true);
+  // a coarse image is carried only if it exists: one that does not (never built, or its allocation failed) is built over
+  // every row when a batch first needs it — a zero-filled one here would be scanned as if it held the stored rows
+  if (rc == ANR_OK && h->x12) rc = dev_alloc(&nx12, ncap * h->dimp * 3 / 8, true);
+  if (rc == ANR_OK && h->x8) rc = dev_alloc(&nx8, ncap / kTileRows * h->kb * kX8TileBytesPerKb, true);
   if (rc == ANR_OK && h->metric == ANR_METRIC_L2) rc = dev_alloc(&nbias, ncap, true);
   if (rc == ANR_OK && h->ntotal > 0) {
     const int64_t used = round_up(h->ntotal, kTileRows);
@@ -199,8 +206,10 @@ int grow_storage(anr_index *h, int64_t need_rows) {
                                   h->stream);
     if (e == hipSuccess)
       e = hipMemcpyAsync(nx16, h->x16, (size_t)used * h->dimp * sizeof(_Float16), hipMemcpyDeviceToDevice, h->stream);
-    if (e == hipSuccess && nx12 && h->x12)
+    if (e == hipSuccess && nx12)
       e = hipMemcpyAsync(nx12, h->x12, (size_t)used * h->dimp * 3 / 2, hipMemcpyDeviceToDevice, h->stream);
+    if (e == hipSuccess && nx8)
+      e = hipMemcpyAsync(nx8, h->x8, (size_t)(used / kTileRows) * h->kb * kX8TileBytesPerKb, hipMemcpyDeviceToDevice, h->stream);
     if (e == hipSuccess && nbias)
       e = hipMemcpyAsync(nbias, h->rowbias, (size_t)h->ntotal * sizeof(float), hipMemcpyDeviceToDevice, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
@@ -210,16 +219,19 @@ int grow_storage(anr_index *h, int64_t need_rows) {
     dev_free(nx32);
     dev_free(nx16);
     dev_free(nx12);
+    dev_free(nx8);
     dev_free(nbias);
     return rc;
   }
   dev_free(h->x32);
   dev_free(h->x16);
   dev_free(h->x12);
+  dev_free(h->x8);
   dev_free(h->rowbias);
   h->x32 = nx32;
   h->x16 = nx16;
   h->x12 = nx12;
+  h->x8 = nx8;
   h->rowbias = nbias;
   h->cap = ncap;
   return ANR_OK;
@@ -337,7 +349,8 @@ int launch_post(int nblocks, const SelParams &sp, const PostParams &pp, hipStrea
   return ANR_OK;
 }
 
-template <bool DENSE, bool F12 = false>
+// BITS: the image the scan reads (16: x16, 12: x12, 8: x8)
+template <bool DENSE, int BITS = 16>
 int launch_scan(anr_index *h, const ScanParams &p, hipStream_t st, int max_grid, int *grid_out = nullptr) {
   if (p.n_tiles <= 0) return ANR_OK;
   const size_t lds = (size_t)2 * p.kb * 64 * 16 + kQB * kLadder * 8 + kQB * 8;
@@ -354,10 +367,13 @@ int launch_scan(anr_index *h, const ScanParams &p, hipStream_t st, int max_grid,
   if (grid_out) *grid_out = (int)grid;
   // a pass over more than the Infinity Cache can hold streams with non-temporal loads
   const bool stream = p.tile_stride == 1 && p.n_tiles * (int64_t)p.kb * 1024 > ((int64_t)192 << 20);
-#define ANR_LAUNCH_SCAN(CHV, STRV)                                                             \
-  {                                                                                            \
-    ANR_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(k_scan<DENSE, CHV, 768, STRV, F12>), 160 * 1024)); \
-    hipLaunchKernelGGL((k_scan<DENSE, CHV, 768, STRV, F12>), dim3((unsigned)grid), dim3(nt), lds, st, p); \
+#define ANR_LAUNCH_SCAN(CHV, STRV)                                                                                 \
+  if (BITS == 8) {                                                                                                 \
+    ANR_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(k_scan8<DENSE, CHV, 768, STRV>), 160 * 1024));      \
+    hipLaunchKernelGGL((k_scan8<DENSE, CHV, 768, STRV>), dim3((unsigned)grid), dim3(nt), lds, st, p);             \
+  } else {                                                                                                         \
+    ANR_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(k_scan<DENSE, CHV, 768, STRV, BITS == 12>), 160 * 1024)); \
+    hipLaunchKernelGGL((k_scan<DENSE, CHV, 768, STRV, BITS == 12>), dim3((unsigned)grid), dim3(nt), lds, st, p); \
   }
   if (p.kb % 16 == 0) {
     if (stream) ANR_LAUNCH_SCAN(8, true) else ANR_LAUNCH_SCAN(8, false)
@@ -382,6 +398,17 @@ int refresh_xstat(anr_index *h);
 // ANR_OPT_SCAN_BITS 0: indexes of at least this many rows scan the 12-bit image (768-d, batch 64, pipelined, 16 -> 12 bits:
 // 131 072 rows 0.051 -> 0.051 ms per batch, 262 144 rows 0.089 -> 0.077, 500 000 rows 0.149 -> 0.124)
 constexpr int64_t kAuto12Rows = 262144;
+// ... and from this many rows on the 8-bit image
+constexpr int64_t kAuto8Rows = 2097152;
+
+// the image a batch of this index wants to scan (16, 12 or 8 bits), before memory and corpus-size checks
+int wanted_bits(const anr_index *h) {
+  if (h->f12_suspended) return 16;
+  if (h->scan_bits != 0) return h->scan_bits;
+  return h->ntotal >= kAuto8Rows ? 8 : (h->ntotal >= kAuto12Rows ? 12 : 16);
+}
+
+int64_t x8_bytes(const anr_index *h) { return h->cap / kTileRows * h->kb * kX8TileBytesPerKb; }
 
 // the 12-bit image of what is stored (later adds keep it up to date); the caller has drained the pipeline or is about to
 // enqueue on a stream that follows h->stream's work
@@ -404,11 +431,33 @@ int build_x12(anr_index *h) {
   return refresh_xstat(h);
 }
 
-// K' of a 12-bit batch = the base (256 at k = 100) x kF12Steps[level] / 4
+// the 8-bit image of what is stored, from x32 (later adds keep it up to date); same contract as build_x12
+int build_x8(anr_index *h) {
+  if (h->x8 || h->cap <= 0) return ANR_OK;
+  hipError_t e = hipMalloc(reinterpret_cast<void **>(&h->x8), (size_t)x8_bytes(h));
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    h->x8 = nullptr;
+    return fail(ANR_EHIP, "no memory for the 8-bit image: %s", hipGetErrorString(e));
+  }
+  ANR_HIP(hipMemsetAsync(h->x8, 0, (size_t)x8_bytes(h), h->stream));
+  if (h->ntotal > 0) {
+    Build8Params bp{h->x32, h->x8, h->ntotal, h->dim, h->kb, h->xstat};
+    hipLaunchKernelGGL(k_build8, dim3((unsigned)ceil_div(h->ntotal, kTileRows)), dim3(256), 0, h->stream, bp);
+    ANR_HIP(hipGetLastError());
+  }
+  ANR_HIP(hipStreamSynchronize(h->stream));
+  h->xstat_dirty = true;
+  return refresh_xstat(h);
+}
+
+// K' of a coarse-image batch = the base (256 at k = 100) x steps[level] / 4: kF12Steps for the 12-bit image, kF8Steps for
+// the 8-bit one, whose error term is ~1.7x the 12-bit one
 constexpr int kF12Steps[] = {4, 6, 8, 10, 12, 16};
+constexpr int kF8Steps[] = {5, 6, 8, 10, 12, 16};
 constexpr int kF12Levels = 6;
 
-int auto_overfetch(const anr_index *h, int k, bool f12 = false) {
+int auto_overfetch(const anr_index *h, int k, bool f12 = false, int bits = 12) {
   if (h->overfetch > 0) {
     int m = h->overfetch < k ? k : h->overfetch;
     return m > kMaxSel ? kMaxSel : m;
@@ -418,7 +467,8 @@ int auto_overfetch(const anr_index *h, int k, bool f12 = false) {
   // Gaussian corpus failing, 256 none (and 320 / 384 cost more than they save: 1.737 / 1.770 / 1.776 ms per batch)
   if (f12) {
     extra = k > 64 ? k : 64;
-    const int m = (int)round_up((round_up(k + extra, 64) * kF12Steps[h->f12_level]) / 4, 64);
+    const int step = bits == 8 ? kF8Steps[h->f12_level] : kF12Steps[h->f12_level];
+    const int m = (int)round_up((round_up(k + extra, 64) * step) / 4, 64);
     return m > kMaxSel ? kMaxSel : m;
   }
   int m = (int)round_up(k + extra, 64) * h->overfetch_boost;
@@ -819,11 +869,15 @@ int enqueue_batch(anr_index *h, const float *q_dev, int nq, int k, int64_t out_o
   // the image the streaming pass reads (ANR_OPT_SCAN_BITS; 0 = 12 bits from kAuto12Rows rows on: below, a batch is
   // mostly its side kernels).  The sample and every recovery scan read x16; the certificate of a 12-bit batch takes the
   // statistics of the coarser image (pp.xstat / fp.xstat below).
-  bool f12 = false;
-  if (!h->f12_suspended && (h->scan_bits == 12 || (h->scan_bits == 0 && h->ntotal >= kAuto12Rows))) {
+  int bits = wanted_bits(h);
+  if (bits == 12) {
     if (!h->x12 && !h->x12_no_memory && build_x12(h) != ANR_OK) h->x12_no_memory = true;  // (stays on the f16 image)
-    f12 = h->x12 != nullptr;
+    if (!h->x12) bits = 16;
+  } else if (bits == 8) {
+    if (!h->x8 && !h->x12_no_memory && build_x8(h) != ANR_OK) h->x12_no_memory = true;
+    if (!h->x8) bits = 16;
   }
+  bool f12 = bits != 16;
   const int64_t n_tiles = ceil_div(h->ntotal, kTileRows);
   const int64_t full_tiles = h->ntotal / kTileRows;
   // threshold sample: ~1/64 of the rows, between 4K and 16K (more rows -> tighter first threshold)
@@ -836,9 +890,10 @@ int enqueue_batch(anr_index *h, const float *q_dev, int nq, int k, int64_t out_o
   // tile maxima: the M-th largest is backed by M distinct rows -> at least 2 M sample tiles; the threshold-gated pipeline
   // needs a corpus of eight samples.  A 12-bit batch's larger K' can push a mid-sized corpus below that: it then runs as an
   // f16 batch (the small-corpus path scores every row from x16) with the f16 K'.
-  int M = auto_overfetch(h, k, f12);
+  int M = auto_overfetch(h, k, f12, bits);
   if (f12 && full_tiles < 8 * std::max<int64_t>(sample_want, 2 * (int64_t)M)) {
     f12 = false;
+    bits = 16;
     M = auto_overfetch(h, k, false);
   }
   w.M = M;
@@ -967,10 +1022,14 @@ int enqueue_batch(anr_index *h, const float *q_dev, int nq, int k, int64_t out_o
     }
     if (w.timed) ANR_HIP(hipEventRecord(w.ev_t0, ms));
     w.f12 = f12;
+    w.bits = bits;
     w.f12_level = h->f12_level;
-    if (f12) {
+    if (bits == 8) {
+      sc.x8 = h->x8;
+      ANR_TRY((launch_scan<false, 8>(h, sc, ms, scan_grid_max, &scan_grid)));
+    } else if (bits == 12) {
       sc.x12 = h->x12;
-      ANR_TRY((launch_scan<false, true>(h, sc, ms, scan_grid_max, &scan_grid)));
+      ANR_TRY((launch_scan<false, 12>(h, sc, ms, scan_grid_max, &scan_grid)));
     } else {
       ANR_TRY(launch_scan<false>(h, sc, ms, scan_grid_max, &scan_grid));
     }
@@ -980,7 +1039,7 @@ int enqueue_batch(anr_index *h, const float *q_dev, int nq, int k, int64_t out_o
       ANR_HIP(hipEventRecord(w.ev_scan, ms));
       ANR_HIP(hipStreamWaitEvent(ps, w.ev_scan, 0));
     }
-    w.scan_bytes = n_tiles * kTileRows * (int64_t)h->dimp * (f12 ? 3 : 4) / 2;
+    w.scan_bytes = bits == 8 ? n_tiles * h->kb * kX8TileBytesPerKb : n_tiles * kTileRows * (int64_t)h->dimp * (f12 ? 3 : 4) / 2;
     // post
     sp.cand = w.cand;
     sp.cntb = w.cntb;
@@ -1001,7 +1060,7 @@ int enqueue_batch(anr_index *h, const float *q_dev, int nq, int k, int64_t out_o
     pp.dimp = h->dimp;
     pp.metric = h->metric;
     pp.qstat = w.qstat;
-    pp.xstat = (sparse && w.f12) ? h->xstat12 : h->xstat;
+    pp.xstat = (sparse && w.f12) ? (w.bits == 8 ? h->xstat8 : h->xstat12) : h->xstat;
     pp.overflow = sparse ? w.ncand + kQB : nullptr;
     pp.ncand = sparse ? w.ncand : nullptr;
     pp.n_rows = h->ntotal;
@@ -1059,7 +1118,7 @@ int enqueue_batch(anr_index *h, const float *q_dev, int nq, int k, int64_t out_o
   fp.sel_m = w.sel_m;
   fp.overflow = sparse ? w.ncand + kQB : nullptr;
   fp.qstat = w.qstat;
-  fp.xstat = (sparse && w.f12) ? h->xstat12 : h->xstat;
+  fp.xstat = (sparse && w.f12) ? (w.bits == 8 ? h->xstat8 : h->xstat12) : h->xstat;
   fp.metric = h->metric;
   fp.dimp = h->dimp;
   fp.n_rows = h->ntotal;
@@ -1089,13 +1148,15 @@ int enqueue_batch(anr_index *h, const float *q_dev, int nq, int k, int64_t out_o
 
 int refresh_xstat(anr_index *h) {
   if (!h->xstat_dirty) return ANR_OK;
-  unsigned host[4] = {0, 0, 0, 0};
+  unsigned host[5] = {0, 0, 0, 0, 0};
   ANR_HIP(hipStreamSynchronize(h->stream));
   ANR_HIP(hipMemcpy(host, h->xstat, sizeof host, hipMemcpyDeviceToHost));
   h->f16_unusable = host[2] != 0;
   // (norms are floats >= 0: their bit patterns order like the values)
   const unsigned pair[2] = {host[0], host[1] > host[3] ? host[1] : host[3]};
   ANR_HIP(hipMemcpy(h->xstat12, pair, sizeof pair, hipMemcpyHostToDevice));
+  const unsigned pair8[2] = {host[0], host[1] > host[4] ? host[1] : host[4]};
+  ANR_HIP(hipMemcpy(h->xstat8, pair8, sizeof pair8, hipMemcpyHostToDevice));
   h->xstat_dirty = false;
   return ANR_OK;
 }
@@ -1413,7 +1474,8 @@ int add_impl(anr_index *h, const float *x_dev, int64_t n, hipStream_t st) {
   ap.x16 = h->x16;
   ap.rowbias = h->rowbias;
   ap.stat = h->xstat;
-  ap.x12 = h->x12;  // (kept up to date whenever it exists)
+  ap.x12 = h->x12;  // (kept up to date whenever they exist)
+  ap.x8 = h->x8;
   const int64_t t0 = h->ntotal / kTileRows, t1 = ceil_div(h->ntotal + n, kTileRows);
   hipLaunchKernelGGL(k_add, dim3((unsigned)(t1 - t0)), dim3(256), 0, st, ap);
   ANR_HIP(hipGetLastError());
@@ -1488,8 +1550,9 @@ int anr_index_create(int32_t dim, int32_t metric, int32_t normalize, int32_t dev
       return fail(ANR_EHIP, "hipStreamCreate failed: %s", hipGetErrorString(e));
     }
   }
-  int r = dev_alloc(&h->xstat, 4, true);
+  int r = dev_alloc(&h->xstat, 5, true);
   if (r == ANR_OK) r = dev_alloc(&h->xstat12, 2, true);
+  if (r == ANR_OK) r = dev_alloc(&h->xstat8, 2, true);
   if (r != ANR_OK) {
     anr_index_destroy(h);
     return r;
@@ -1508,7 +1571,9 @@ int anr_index_destroy(anr_index *h) {
   dev_free(h->rowbias);
   dev_free(h->xstat);
   dev_free(h->xstat12);
+  dev_free(h->xstat8);
   dev_free(h->x12);
+  dev_free(h->x8);
   free_workspaces(h);
   dev_free(h->xdense);
   free_largek(&h->largek);
@@ -1583,8 +1648,9 @@ int anr_index_reset(anr_index *h) {
   ANR_HIP(hipStreamSynchronize(h->stream));
   if (h->x16) ANR_HIP(hipMemset(h->x16, 0, (size_t)h->cap * h->dimp * sizeof(_Float16)));
   if (h->x12) ANR_HIP(hipMemset(h->x12, 0, (size_t)h->cap * h->dimp * 3 / 2));
+  if (h->x8) ANR_HIP(hipMemset(h->x8, 0, (size_t)x8_bytes(h)));
   if (h->rowbias) ANR_HIP(hipMemset(h->rowbias, 0, (size_t)h->cap * sizeof(float)));
-  ANR_HIP(hipMemset(h->xstat, 0, 4 * sizeof(unsigned)));
+  ANR_HIP(hipMemset(h->xstat, 0, 5 * sizeof(unsigned)));
   ANR_HIP(hipStreamSynchronize(nullptr));  // the fills run on the NULL stream; later adds use the handle's own
   h->ntotal = 0;
   h->xstat_dirty = true;
@@ -1606,15 +1672,16 @@ int anr_index_reconstruct(anr_index *h, int64_t i0, int64_t n, float *out_host) 
 
 int anr_index_reconstruct_scan_image(anr_index *h, int32_t bits, int64_t i0, int64_t n, float *out_host) {
   if (!h || !out_host || i0 < 0 || n < 0 || i0 + n > h->ntotal) return fail(ANR_EINVAL, "row range out of bounds");
-  if (bits != 12 && bits != 16) return fail(ANR_EINVAL, "bits must be 12 or 16");
+  if (bits != 8 && bits != 12 && bits != 16) return fail(ANR_EINVAL, "bits must be 8, 12 or 16");
   if (bits == 12 && !h->x12) return fail(ANR_ESTATE, "the index keeps no 12-bit image (ANR_OPT_SCAN_BITS)");
+  if (bits == 8 && !h->x8) return fail(ANR_ESTATE, "the index keeps no 8-bit image (ANR_OPT_SCAN_BITS)");
   if (n == 0) return ANR_OK;
   DeviceGuard g(h->device);
   std::lock_guard<std::mutex> lk(h->mu);
   ANR_TRY(drain(h));
   float *d = nullptr;
   ANR_TRY(dev_alloc(&d, n * h->dim, false));
-  ImageRowsParams ip{h->x16, bits == 12 ? h->x12 : nullptr, i0, n, h->dim, h->kb, d};
+  ImageRowsParams ip{h->x16, bits == 12 ? h->x12 : nullptr, bits == 8 ? h->x8 : nullptr, i0, n, h->dim, h->kb, d};
   hipLaunchKernelGGL(k_image_rows, dim3((unsigned)ceil_div(n * h->kb * 2, 256)), dim3(256), 0, h->stream, ip);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
@@ -1637,11 +1704,25 @@ int anr_index_scan_image_stats(anr_index *h, int32_t *bits_in_use, float *max_no
     std::memcpy(&v, &u, 4);
     return v;
   };
-  const bool f12 = h->x12 && !h->f12_suspended && (h->scan_bits == 12 || (h->scan_bits == 0 && h->ntotal >= kAuto12Rows));
-  if (bits_in_use) *bits_in_use = f12 ? 12 : 16;
+  const int want = wanted_bits(h);
+  if (bits_in_use) *bits_in_use = (want == 12 && h->x12) ? 12 : ((want == 8 && h->x8) ? 8 : 16);
   if (max_norm) *max_norm = f(host[0]);
   if (max_err16) *max_err16 = f(host[1]);
   if (max_err12) *max_err12 = h->x12 ? f(host[3]) : 0.0f;
+  return ANR_OK;
+}
+
+int anr_index_scan_image_err8(anr_index *h, float *max_err8) {
+  if (!h || !max_err8) return fail(ANR_EINVAL, "null argument");
+  DeviceGuard g(h->device);
+  std::lock_guard<std::mutex> lk(h->mu);
+  ANR_TRY(drain(h));
+  unsigned host[5] = {0, 0, 0, 0, 0};
+  ANR_HIP(hipStreamSynchronize(h->stream));
+  ANR_HIP(hipMemcpy(host, h->xstat, sizeof host, hipMemcpyDeviceToHost));
+  float v;
+  std::memcpy(&v, &host[4], 4);
+  *max_err8 = h->x8 ? v : 0.0f;
   return ANR_OK;
 }
 
@@ -1928,7 +2009,8 @@ int anr_index_set_option(anr_index *h, int32_t opt, int64_t value) {
     case ANR_OPT_SCHEDULE: h->schedule = value != 0; break;
     case ANR_OPT_STREAM_WAIT: h->stream_wait = value != 0; break;
     case ANR_OPT_SCAN_BITS: {
-      if (value != 0 && value != 12 && value != 16) return fail(ANR_EINVAL, "scan bits must be 0 (auto), 12 or 16");
+      if (value != 0 && value != 8 && value != 12 && value != 16)
+        return fail(ANR_EINVAL, "scan bits must be 0 (auto), 8, 12 or 16");
       h->f12_suspended = false;
       h->x12_no_memory = false;
       h->f12_strikes = h->f12_level = h->f12_clean = h->f12_lowered = 0;
@@ -1936,9 +2018,12 @@ int anr_index_set_option(anr_index *h, int32_t opt, int64_t value) {
       if ((int)value == h->scan_bits) break;
       ANR_TRY(drain(h));
       ANR_HIP(hipStreamSynchronize(h->stream));
-      h->scan_bits = (int)value;
-      if (value == 16) dev_free(h->x12);
+      // only the image in use is kept; the new one is committed once it is built
       if (value == 12 && !h->x12 && h->cap > 0) ANR_TRY(build_x12(h));
+      if (value == 8 && !h->x8 && h->cap > 0) ANR_TRY(build_x8(h));
+      h->scan_bits = (int)value;
+      if (value != 12 && value != 0) dev_free(h->x12);
+      if (value != 8 && value != 0) dev_free(h->x8);
       break;
     }
     case ANR_OPT_STREAMS:

@@ -12,6 +12,13 @@
 //                                      elements 4-7, and the eight low nibbles (elements 0-3 in the low nibbles of bytes
 //                                      0-3, elements 4-7 in the high nibbles) — seven vector instructions turn them back
 //                                      into the 16-byte f16 operand (x12_unpack);
+//   x8   [cap/32][KB/2 pairs][64][16 B] + [32 rows][KB/2] f16
+//                                      optional (ANR_OPT_SCAN_BITS 8): int8 codes with one f16 scale per row and 32 dims (a
+//                                      pair of k-blocks), 1.0625 B per value.  A tile is kb * 544 bytes: first the codes,
+//                                      per pair 64 lanes x 16 B — lane l = r + 32 h holds row r's elements 8h..8h+7 of the
+//                                      pair's first k-block (bytes 0-7), then of its second (bytes 8-15), each code c stored
+//                                      as the byte c + 128 — then the scales, row-major: row r's scale of pair m at byte
+//                                      kb * 512 + r * kb + 2 m of the tile.  Decoded value f16(s * c) (x8_operand);
 //   q16  [2][KB][64 lanes][8]          f16, the 64 queries of a batch in the B-operand layout.
 // KB = dimp/16 with dimp = dim rounded up to 128.
 #pragma once
@@ -95,6 +102,76 @@ __device__ __forceinline__ uint4 x12_unpack(unsigned h0, unsigned h1, unsigned n
   return o;
 }
 
+// ---- the 8-bit image (ANR_OPT_SCAN_BITS 8) ----------------------------------------------------------------------------
+// Per row and 32-dim group: s = f16(absmax / 127), one f16 step up if s * 127 < absmax (an all-zero group keeps s = 0);
+// c = clamp(rint(x / s), -cmax, cmax) with cmax = min(127, floor(65504 / s)) so that s * c stays finite; decoded value
+// f16(s * c), one rounding.
+constexpr int kX8TileBytesPerKb = 544;  // codes 512 + scales 32 per k-block of a 32-row tile
+__device__ __forceinline__ unsigned short x8_scale(float absmax) {
+  _Float16 s = (_Float16)(absmax / 127.0f);
+  if ((float)s * 127.0f < absmax) {
+    const unsigned short b = __builtin_bit_cast(unsigned short, s);
+    s = __builtin_bit_cast(_Float16, (unsigned short)(b + 1u));  // s >= 0: the next f16 up
+  }
+  return __builtin_bit_cast(unsigned short, s);
+}
+// the stored byte of x under scale bits sb
+__device__ __forceinline__ unsigned x8_code(float x, unsigned short sb) {
+  const float s = (float)__builtin_bit_cast(_Float16, sb);
+  if (!(s > 0.0f)) return 128u;
+  const float cmax = fminf(127.0f, floorf(__fdiv_rn(65504.0f, s)));
+  const float c = fminf(cmax, fmaxf(-cmax, rintf(__fdiv_rn(x, s))));
+  return (unsigned)((int)c + 128);
+}
+typedef _Float16 half2v __attribute__((ext_vector_type(2)));
+// eight codes (two words, element 2 j / 2 j + 1 in bytes 2 j / 2 j + 1 ... of the pair of words) and the scale as {s, s} ->
+// the f16 operand.  v_perm_b32 sets each code byte u under the byte 0x64: the f16 1024 + u; minus 1152 is c, exactly; times
+// s is f16(s * c), one rounding.
+__device__ __forceinline__ half8 x8_operand(unsigned w0, unsigned w1, half2v ss) {
+  const half2v bias = {(_Float16)-1152.0f, (_Float16)-1152.0f};
+  const unsigned k = 0x64646464u;
+  const unsigned v0 = __builtin_amdgcn_perm(k, w0, 0x04010400u), v1 = __builtin_amdgcn_perm(k, w0, 0x04030402u);
+  const unsigned v2 = __builtin_amdgcn_perm(k, w1, 0x04010400u), v3 = __builtin_amdgcn_perm(k, w1, 0x04030402u);
+  const half2v o0 = (__builtin_bit_cast(half2v, v0) + bias) * ss, o1 = (__builtin_bit_cast(half2v, v1) + bias) * ss;
+  const half2v o2 = (__builtin_bit_cast(half2v, v2) + bias) * ss, o3 = (__builtin_bit_cast(half2v, v3) + bias) * ss;
+  half8 o;
+  o[0] = o0[0]; o[1] = o0[1]; o[2] = o1[0]; o[3] = o1[1];
+  o[4] = o2[0]; o[5] = o2[1]; o[6] = o3[0]; o[7] = o3[1];
+  return o;
+}
+// {s, s} from the scale half `hi` of a word holding two scales
+__device__ __forceinline__ half2v x8_splat(unsigned w, int hi) {
+  return __builtin_bit_cast(half2v, __builtin_amdgcn_perm(w, w, hi ? 0x03020302u : 0x01000100u));
+}
+// one row's 32-value group (v[0..31] = dims 32 m .. 32 m + 31, zeros past the row) -> its scale bits, the two 16-byte lane
+// words (lane r: dims 0-7 and 16-23; lane r + 32: dims 8-15 and 24-31) and the squared error of the decoded values
+__device__ __forceinline__ float x8_group(const float *v, int vstride, unsigned short *scale, uint4 *lane_lo, uint4 *lane_hi) {
+  float amax = 0.0f;
+  for (int j = 0; j < 32; ++j) amax = fmaxf(amax, fabsf(v[j * vstride]));
+  const unsigned short sb = amax > 0.0f ? x8_scale(amax) : (unsigned short)0;
+  const half2v ss = __builtin_bit_cast(half2v, (unsigned)sb | ((unsigned)sb << 16));
+  unsigned w[8];
+  for (int i = 0; i < 8; ++i) {
+    // word i: h = (i >> 1) & 1 ... lane_lo words 0-1 = dims 0-7, 2-3 = dims 16-23; lane_hi 0-1 = dims 8-15, 2-3 = 24-31
+    const int d0 = (i < 4 ? 0 : 8) + ((i & 2) ? 16 : 0) + 4 * (i & 1);
+    w[i] = 0;
+    for (int b = 0; b < 4; ++b) w[i] |= x8_code(v[(d0 + b) * vstride], sb) << (8 * b);
+  }
+  float e2 = 0.0f;
+  for (int i = 0; i < 8; i += 2) {
+    const half8 o = x8_operand(w[i], w[i + 1], ss);
+    const int d0 = (i < 4 ? 0 : 8) + ((i & 2) ? 16 : 0);
+    for (int j = 0; j < 8; ++j) {
+      const float d = (float)o[j] - v[(d0 + j) * vstride];
+      e2 += d * d;
+    }
+  }
+  *scale = sb;
+  *lane_lo = make_uint4(w[0], w[1], w[2], w[3]);
+  *lane_hi = make_uint4(w[4], w[5], w[6], w[7]);
+  return e2;
+}
+
 // ------------------------------------------------------------------------------------------------
 // add: normalise (optional), store x32, convert to the blocked f16 image, track norm / error maxima
 // ------------------------------------------------------------------------------------------------
@@ -108,8 +185,10 @@ struct AddParams {
   _Float16 *x16;
   float *rowbias;     // [cap] -0.5*||x||^2 of the stored row (L2 metric) or nullptr
   unsigned *stat;     // [0] max ||x|| bits, [1] max ||x16 - x|| bits (floats >= 0, so uint order == float
-                      // order), [2] != 0 when some |x| exceeds the f16 range (scan disabled), [3] max ||x12 - x|| bits
+                      // order), [2] != 0 when some |x| exceeds the f16 range (scan disabled), [3] max ||x12 - x|| bits,
+                      // [4] max ||x8 - x|| bits
   unsigned *x12;      // optional 12-bit image (see the top of this file)
+  unsigned char *x8;  // optional 8-bit image
 };
 
 // one block (256 threads) per 32-row tile that receives rows
@@ -117,6 +196,7 @@ __global__ __launch_bounds__(256) void k_add(AddParams p) {
   __shared__ float s_scale[kTileRows];
   __shared__ float s_err[kTileRows];
   __shared__ float s_err12[kTileRows];
+  __shared__ float s_err8[kTileRows];
   __shared__ float s_n2[kTileRows];
   __shared__ float s_x[kTileRows][132];
 
@@ -144,6 +224,7 @@ __global__ __launch_bounds__(256) void k_add(AddParams p) {
       s_scale[r] = scale;
       s_err[r] = 0.0f;
       s_err12[r] = 0.0f;
+      s_err8[r] = 0.0f;
       s_n2[r] = 0.0f;
     }
   }
@@ -202,6 +283,23 @@ __global__ __launch_bounds__(256) void k_add(AddParams p) {
         atomicAdd(&s_n2[r], n2);
       }
     }
+    if (p.x8) {
+      // one thread per (row, 32-dim group) of the stage
+      for (int i = tid; i < kTileRows * 4; i += 256) {
+        const int r = i & 31, g = i >> 5;
+        const int64_t src = trow0 + r - p.row0;
+        if (src < 0 || src >= p.n) continue;
+        unsigned short sb;
+        uint4 lo, hi;
+        const float e8 = x8_group(&s_x[r][g * 32], 1, &sb, &lo, &hi);
+        const int m = (k0 >> 5) + g;
+        unsigned char *t = p.x8 + tile * p.kb * kX8TileBytesPerKb;
+        *reinterpret_cast<uint4 *>(t + (int64_t)m * 1024 + r * 16) = lo;
+        *reinterpret_cast<uint4 *>(t + (int64_t)m * 1024 + (r + 32) * 16) = hi;
+        *reinterpret_cast<unsigned short *>(t + (int64_t)p.kb * 512 + r * p.kb + 2 * m) = sb;
+        atomicAdd(&s_err8[r], e8);
+      }
+    }
     __syncthreads();
   }
   if (tid < kTileRows) {
@@ -212,6 +310,7 @@ __global__ __launch_bounds__(256) void k_add(AddParams p) {
       atomicMax(&p.stat[0], __float_as_uint(sqrtf(s_n2[tid]) * 1.0001f));
       atomicMax(&p.stat[1], __float_as_uint(sqrtf(s_err[tid]) * 1.0001f));
       if (p.x12) atomicMax(&p.stat[3], __float_as_uint(sqrtf(s_err12[tid]) * 1.0001f));
+      if (p.x8) atomicMax(&p.stat[4], __float_as_uint(sqrtf(s_err8[tid]) * 1.0001f));
       if (p.rowbias) p.rowbias[grow] = -0.5f * s_n2[tid];
     }
   }
@@ -261,11 +360,48 @@ __global__ __launch_bounds__(256) void k_build12(Build12Params p) {
     atomicMax(&p.stat[3], __float_as_uint(sqrtf(s_err12[tid]) * 1.0001f));
 }
 
+// the 8-bit image of rows that are already stored, from x32: one block per 32-row tile, one thread per (row, 32-dim group)
+struct Build8Params {
+  const float *x32;
+  unsigned char *x8;
+  int64_t n_rows;
+  int dim, kb;
+  unsigned *stat;  // [4] max ||x8 - x||
+};
+__global__ __launch_bounds__(256) void k_build8(Build8Params p) {
+  __shared__ float s_err8[kTileRows];
+  const int tid = threadIdx.x;
+  const int64_t tile = blockIdx.x;
+  if (tid < kTileRows) s_err8[tid] = 0.0f;
+  __syncthreads();
+  unsigned char *t = p.x8 + tile * p.kb * kX8TileBytesPerKb;
+  for (int i = tid; i < kTileRows * (p.kb >> 1); i += 256) {
+    const int r = i & 31, m = i >> 5;
+    const int64_t grow = tile * kTileRows + r;
+    float v[32];
+    for (int j = 0; j < 32; ++j) {
+      const int k = m * 32 + j;
+      v[j] = (grow < p.n_rows && k < p.dim) ? p.x32[grow * p.dim + k] : 0.0f;
+    }
+    unsigned short sb;
+    uint4 lo, hi;
+    const float e8 = x8_group(v, 1, &sb, &lo, &hi);
+    *reinterpret_cast<uint4 *>(t + (int64_t)m * 1024 + r * 16) = lo;
+    *reinterpret_cast<uint4 *>(t + (int64_t)m * 1024 + (r + 32) * 16) = hi;
+    *reinterpret_cast<unsigned short *>(t + (int64_t)p.kb * 512 + r * p.kb + 2 * m) = sb;
+    if (grow < p.n_rows) atomicAdd(&s_err8[r], e8);
+  }
+  __syncthreads();
+  if (tid < kTileRows && tile * kTileRows + tid < p.n_rows)
+    atomicMax(&p.stat[4], __float_as_uint(sqrtf(s_err8[tid]) * 1.0001f));
+}
+
 // the image the streaming scan reads, decoded back to float32 rows (anr_index_reconstruct_scan_image: how the tests pin the
 // 12-bit image and its tracked error norm against the oracle's restatement).  One thread per (row, 8 values).
 struct ImageRowsParams {
   const _Float16 *x16;
-  const unsigned *x12;  // nullptr: decode the f16 image
+  const unsigned *x12;  // nullptr: decode the f16 image (or x8)
+  const unsigned char *x8;
   int64_t i0, n;
   int dim, kb;
   float *out;           // [n][dim]
@@ -283,6 +419,11 @@ __global__ __launch_bounds__(256) void k_image_rows(ImageRowsParams p) {
   if (p.x12) {
     const unsigned *w = p.x12 + (blk * 64 + l) * 3;
     hv = __builtin_bit_cast(half8, x12_unpack(w[0], w[1], w[2]));
+  } else if (p.x8) {
+    const unsigned char *t = p.x8 + tile * p.kb * kX8TileBytesPerKb;
+    const unsigned *w = reinterpret_cast<const unsigned *>(t + (int64_t)(kbl >> 1) * 1024 + l * 16 + (kbl & 1) * 8);
+    const unsigned short sb = *reinterpret_cast<const unsigned short *>(t + (int64_t)p.kb * 512 + (l & 31) * p.kb + 2 * (kbl >> 1));
+    hv = x8_operand(w[0], w[1], __builtin_bit_cast(half2v, (unsigned)sb | ((unsigned)sb << 16)));
   } else {
     hv = *reinterpret_cast<const half8 *>(p.x16 + (blk * 64 + l) * 8);
   }
@@ -384,6 +525,7 @@ __global__ __launch_bounds__(256) void k_prepq(PrepQParams p) {
 struct ScanParams {
   const uint4 *x16;
   const unsigned *x12;  // the 12-bit image (k_scan<.., F12 = true> reads it instead of x16)
+  const unsigned char *x8;  // the 8-bit image (k_scan8 reads it)
   const uint4 *q16;
   int kb;
   int64_t n_rows;
@@ -487,6 +629,88 @@ __device__ __forceinline__ void scan_mfma_refill(ScanOp<F12> (&a)[CH], const cha
   }
 }
 
+// A chunk of CH k-blocks of one tile, as the k-loop of the scan sees it: `x` is the lane's pointer to the chunk's codes,
+// `sx` to its scales (8-bit image only; kScaleOffset(kb, lane) from the codes of a tile's first chunk, kScaleChunkBytes per
+// chunk).  The f16 and 12-bit images: CH ScanOps, no scales.
+template <int CH, bool F12>
+struct ScanChunk {
+  ScanOp<F12> a[CH];
+  static constexpr int kLaneBytes = ScanOp<F12>::kLaneBytes;
+  static constexpr int64_t kTileBytesPerKb = 64 * kLaneBytes;
+  static constexpr int64_t kChunkBytes = CH * 64 * kLaneBytes;
+  static constexpr int64_t kScaleChunkBytes = 0;
+  static __device__ __forceinline__ int kScaleOffset(int, int) { return 0; }
+  template <bool STREAM>
+  __device__ __forceinline__ void load(const char *x, const char *) {
+    scan_load<CH, STREAM, F12>(a, x);
+  }
+  __device__ __forceinline__ void mfma(const uint4 *ldsq0, const uint4 *ldsq1, int kbase, floatx16 &acc0, floatx16 &acc1) {
+    scan_mfma<CH, F12>(a, ldsq0, ldsq1, kbase, acc0, acc1);
+  }
+  template <bool STREAM>
+  __device__ __forceinline__ void mfma_refill(const char *x, const char *, const uint4 *ldsq0, const uint4 *ldsq1, int kbase,
+                                              floatx16 &acc0, floatx16 &acc1) {
+    scan_mfma_refill<CH, STREAM, F12>(a, x, ldsq0, ldsq1, kbase, acc0, acc1);
+  }
+};
+// The 8-bit image: CH / 2 pairs of k-blocks, 16 bytes of codes each, and the row's CH / 2 f16 scales of the chunk (one
+// 8- or 4-byte load from the tile's scale block).  The operand is decoded right before its two MFMAs (x8_operand); the
+// next chunk's scales are requested first, so its first pair never waits behind its codes.
+template <int CH>
+struct ScanChunk8 {
+  static_assert(CH == 8 || CH == 4, "chunks of 4 or 8 k-blocks");
+  typedef unsigned su __attribute__((ext_vector_type(CH / 4)));
+  uint4 code[CH / 2];
+  su sc;
+  static constexpr int kLaneBytes = 16;
+  static constexpr int64_t kTileBytesPerKb = kX8TileBytesPerKb;
+  static constexpr int64_t kChunkBytes = CH * 512;
+  static constexpr int64_t kScaleChunkBytes = CH;  // CH / 2 scales of 2 bytes
+  // the lane's scales of a tile's first chunk minus its codes of that chunk (both in the tile): kb * 512 + row * kb - lane * 16
+  static __device__ __forceinline__ int kScaleOffset(int kb, int lane) { return kb * 512 + (lane & 31) * kb - lane * 16; }
+  template <bool STREAM>
+  static __device__ __forceinline__ su load_scales(const char *sx) {
+    const su *p = reinterpret_cast<const su *>(sx);
+    return STREAM ? __builtin_nontemporal_load(p) : *p;
+  }
+  template <bool STREAM>
+  __device__ __forceinline__ void load_code(const char *x, int j) {
+    code[j] = ld16<STREAM>(reinterpret_cast<const uint4 *>(x) + j * 64);
+  }
+  template <bool STREAM>
+  __device__ __forceinline__ void load(const char *x, const char *sx) {
+    sc = load_scales<STREAM>(sx);
+#pragma unroll
+    for (int j = 0; j < CH / 2; ++j) load_code<STREAM>(x, j);
+  }
+  __device__ __forceinline__ void pair_mfma(const uint4 &w, half2v ss, const uint4 *ldsq0, const uint4 *ldsq1, int kb0,
+                                            floatx16 &acc0, floatx16 &acc1) const {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const uint4 b0 = ldsq0[(kb0 + h) * 64];
+      const uint4 b1 = ldsq1[(kb0 + h) * 64];
+      const half8 av = h ? x8_operand(w.z, w.w, ss) : x8_operand(w.x, w.y, ss);
+      acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, __builtin_bit_cast(half8, b0), acc0, 0, 0, 0);
+      acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, __builtin_bit_cast(half8, b1), acc1, 0, 0, 0);
+    }
+  }
+  __device__ __forceinline__ void mfma(const uint4 *ldsq0, const uint4 *ldsq1, int kbase, floatx16 &acc0, floatx16 &acc1) {
+#pragma unroll
+    for (int j = 0; j < CH / 2; ++j) pair_mfma(code[j], x8_splat(sc[j >> 1], j & 1), ldsq0, ldsq1, kbase + 2 * j, acc0, acc1);
+  }
+  template <bool STREAM>
+  __device__ __forceinline__ void mfma_refill(const char *x, const char *sx, const uint4 *ldsq0, const uint4 *ldsq1, int kbase,
+                                              floatx16 &acc0, floatx16 &acc1) {
+    const su cur = sc;
+    sc = load_scales<STREAM>(sx);
+#pragma unroll
+    for (int j = 0; j < CH / 2; ++j) {
+      pair_mfma(code[j], x8_splat(cur[j >> 1], j & 1), ldsq0, ldsq1, kbase + 2 * j, acc0, acc1);
+      load_code<STREAM>(x, j);
+    }
+  }
+};
+
 __device__ __forceinline__ unsigned ld_relaxed(const unsigned *p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -536,8 +760,9 @@ __device__ __forceinline__ void scan_emit(const floatx16 &acc, float tau, int lv
 #else
 #define ANR_SCAN_ATTR
 #endif
-template <bool DENSE, int CH, int NT, bool STREAM, bool F12 = false>
-__global__ __launch_bounds__(NT) ANR_SCAN_ATTR void k_scan(ScanParams p) {
+// the body of k_scan (f16 and 12-bit images) and k_scan8: C is the chunk type (ScanChunk, ScanChunk8)
+template <bool DENSE, int CH, class C, bool STREAM>
+__device__ __forceinline__ void scan_body(const ScanParams &p, const char *image) {
   // LDS: Q operand image [2][kb][64] | ladder [64][L] | list lengths [64] | level [64] | pending [64][L]
   extern __shared__ uint4 lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -573,17 +798,24 @@ __global__ __launch_bounds__(NT) ANR_SCAN_ATTR void k_scan(ScanParams p) {
 
   // the first chunk of a wave's next tile is requested before the current tile's epilogue, so the wave
   // always has loads in flight (the epilogue would otherwise be a bubble in its share of the stream)
-  ScanOp<F12> aA[CH], aB[CH];
-  // the lane's share of one k-block is LB bytes (16: f16 image, 12: 12-bit image); a tile is kb such blocks of 64 lanes
-  constexpr int64_t LB = ScanOp<F12>::kLaneBytes, BLK = 64 * LB;
-  const char *xlane = (F12 ? reinterpret_cast<const char *>(p.x12) : reinterpret_cast<const char *>(p.x16)) + lane * LB;
-  if (wglobal < p.n_tiles) scan_load<CH, STREAM, F12>(aA, xlane + (p.tile0 + wglobal * p.tile_stride) * p.kb * BLK);
+  C aA, aB;
+  // a tile is kb * C::kTileBytesPerKb bytes; the lane's pointer into it is offset by lane * C::kLaneBytes
+  constexpr int64_t CB = C::kChunkBytes, SB = C::kScaleChunkBytes;
+  const int64_t tbytes = p.kb * C::kTileBytesPerKb;
+  const int soff = C::kScaleOffset(p.kb, lane);
+  const char *xlane = image + lane * C::kLaneBytes;
+  if (wglobal < p.n_tiles) {
+    const char *x0 = xlane + (p.tile0 + wglobal * p.tile_stride) * tbytes;
+    aA.template load<STREAM>(x0, x0 + soff);
+  }
   for (int64_t i = wglobal; i < p.n_tiles; i += wtotal) {
     const int64_t tile = p.tile0 + i * p.tile_stride;
-    const char *xa = xlane + tile * p.kb * BLK;
+    const char *xa = xlane + tile * tbytes, *sa = xa + soff;
     // no next tile: re-request this tile's last chunk instead (an L2 hit), which keeps the loop free of
     // conditional loads so the compiler can count the outstanding loads exactly
-    const char *xn = (i + wtotal < p.n_tiles) ? xa + wtotal * p.tile_stride * p.kb * BLK : xa + (int64_t)(p.kb - CH) * BLK;
+    const bool more = i + wtotal < p.n_tiles;
+    const char *xn = more ? xa + wtotal * p.tile_stride * tbytes : xa + (int64_t)(nch - 1) * CB;
+    const char *sn = more ? sa + wtotal * p.tile_stride * tbytes : sa + (int64_t)(nch - 1) * SB;
     floatx16 acc0, acc1;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -591,11 +823,13 @@ __global__ __launch_bounds__(NT) ANR_SCAN_ATTR void k_scan(ScanParams p) {
       acc1[r] = 0.0f;
     }
     for (int c = 0; c < nch; c += 2) {
-      scan_load<CH, STREAM, F12>(aB, xa + (int64_t)(c + 1) * CH * BLK);
+      aB.template load<STREAM>(xa + (int64_t)(c + 1) * CB, sa + (int64_t)(c + 1) * SB);
       __builtin_amdgcn_sched_barrier(0);
-      scan_mfma_refill<CH, STREAM, F12>(aA, (c + 2 < nch) ? xa + (int64_t)(c + 2) * CH * BLK : xn, ldsq0, ldsq1, c * CH, acc0, acc1);
+      const bool in = c + 2 < nch;
+      aA.template mfma_refill<STREAM>(in ? xa + (int64_t)(c + 2) * CB : xn, in ? sa + (int64_t)(c + 2) * SB : sn, ldsq0, ldsq1,
+                                      c * CH, acc0, acc1);
       __builtin_amdgcn_sched_barrier(0);
-      scan_mfma<CH, F12>(aB, ldsq0, ldsq1, (c + 1) * CH, acc0, acc1);
+      aB.mfma(ldsq0, ldsq1, (c + 1) * CH, acc0, acc1);
     }
 
     const int64_t row_base = tile * kTileRows + 4 * half;
@@ -667,6 +901,17 @@ __global__ __launch_bounds__(NT) ANR_SCAN_ATTR void k_scan(ScanParams p) {
     if (tid < kQB && p.lvlmax && lds_lvl[tid] > p.lvl0) atomicMax(p.lvlmax + tid, lds_lvl[tid]);
     if (tid == 0) stamp_max(p.stamps, kStampScanEnd);
   }
+}
+
+template <bool DENSE, int CH, int NT, bool STREAM, bool F12 = false>
+__global__ __launch_bounds__(NT) ANR_SCAN_ATTR void k_scan(ScanParams p) {
+  scan_body<DENSE, CH, ScanChunk<CH, F12>, STREAM>(p, F12 ? reinterpret_cast<const char *>(p.x12) : reinterpret_cast<const char *>(p.x16));
+}
+
+// the scan of the 8-bit image (ANR_OPT_SCAN_BITS 8)
+template <bool DENSE, int CH, int NT, bool STREAM>
+__global__ __launch_bounds__(NT) ANR_SCAN_ATTR void k_scan8(ScanParams p) {
+  scan_body<DENSE, CH, ScanChunk8<CH>, STREAM>(p, reinterpret_cast<const char *>(p.x8));
 }
 
 // ------------------------------------------------------------------------------------------------

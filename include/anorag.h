@@ -71,6 +71,8 @@ int anr_index_reconstruct(anr_index *h, int64_t i0, int64_t n, float *out_host);
  * (max_err12 = 0 without a 12-bit image) — with the image batches currently scan (12 or 16).  Any pointer may be NULL. */
 int anr_index_reconstruct_scan_image(anr_index *h, int32_t bits, int64_t i0, int64_t n, float *out_host);
 int anr_index_scan_image_stats(anr_index *h, int32_t *bits_in_use, float *max_norm, float *max_err16, float *max_err12);
+/* The 8-bit image (bits = 8 above, and bits_in_use 8): its largest ||image row - stored float32 row|| (0 without one). */
+int anr_index_scan_image_err8(anr_index *h, float *max_err8);
 
 /* Search nq queries for the k best rows (vector_index.py:223).  D[nq*k] scores best-first (inner
  * product, or squared L2), I[nq*k] row ids, padded with -1 (and -FLT_MAX / +FLT_MAX scores) when
@@ -168,7 +170,10 @@ int anr_index_set_option(anr_index *h, int32_t opt, int64_t value);
                                      the coarser image's error norm (tracked per index like the f16 one) and K' grows from 192
                                      to 256 at k = 100: the results stay the exact top-k of the float32 rows.  A corpus whose
                                      certificates keep failing at the largest K' (near-duplicate neighbourhoods) goes back to
-                                     the f16 image by itself.  Costs 1.5 bytes per stored value of device memory */
+                                     the f16 image by itself.  Costs 1.5 bytes per stored value of device memory.  8 = int8
+                                     codes with one f16 scale per row and 32 dimensions (1.0625 bytes per value, its own K'
+                                     ladder from 320 at k = 100); 0 picks it from 2 097 152 rows on.  Only the image in use is
+                                     built (with 0, the first search that wants it builds it) */
 
 typedef struct anr_search_stats {
   int64_t n_queries;        /* queries of the last search call                                        */
