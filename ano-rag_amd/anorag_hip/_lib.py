@@ -187,6 +187,26 @@ SIGNATURES = {
         [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p],
     ),
     "anr_encoder_shared_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "anr_ivf_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "anr_ivf_destroy": (C.c_int, [C.c_void_p]),
+    "anr_ivf_train": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64]),
+    "anr_ivf_train_from_centroids": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
+    "anr_ivf_set_centroids": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "anr_ivf_get_centroids": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "anr_ivf_is_trained": (C.c_int, [C.c_void_p]),
+    "anr_ivf_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "anr_ivf_add_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "anr_ivf_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "anr_ivf_search_devq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                      C.c_void_p]),
+    "anr_ivf_set_add_raw": (C.c_int, [C.c_void_p, C.c_int32]),
+    "anr_ivf_ntotal": (C.c_int64, [C.c_void_p]),
+    "anr_ivf_list_sizes": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "anr_ivf_reconstruct": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "anr_ivf_remove": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "anr_ivf_set_spherical": (C.c_int, [C.c_void_p, C.c_int32]),
+    "anr_ivf_assignments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "anr_ivf_last_search_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }
 
 _lib = None

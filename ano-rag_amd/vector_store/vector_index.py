@@ -7,10 +7,14 @@ reference (vector_index.py:9-500); the object it keeps in ``self.index`` is an `
 Differences a maintainer should know (also in INTEGRATION.md):
   * every ``index_type`` (Flat / IVFFlat / IVFPQ / HNSW / LSH) is served by the exact scan, so results are
     those of ``Flat`` (a superset of what the approximate types would return); ``nlist`` / ``nprobe`` /
-    ``is_trained`` keep their bookkeeping semantics;
+    ``is_trained`` keep their bookkeeping semantics — unless the config key ``anorag_hip.ivf`` is true: IVFFlat and
+    IVFPQ are then served by ``anorag_hip.IVFIndex`` (IVF-Flat: device k-means with ``nlist`` lists, ``nprobe`` lists
+    scanned per query, the exact top-k of the probed rows; IVFPQ gets IVF-Flat, there is no product quantiser);
+    single device only (with ``anorag_hip.devices`` the index stays exact);
   * ``save_index`` writes this build's own container (header + float32 rows) under the reference's file
     name ``index_{type}_{dim}d.faiss`` with the same ``_metadata.json`` sidecar; a file written by faiss
-    cannot be read (``load_index`` returns False);
+    cannot be read (``load_index`` returns False); an IVF index appends a trailer (``write_ivf_trailer``) that only
+    a loader with ``anorag_hip.ivf`` on reads;
   * there is no CPU path: with no HIP device ``create_index`` logs the error and returns False.
 """
 from __future__ import annotations
@@ -21,12 +25,41 @@ from typing import Any, Dict, List, Optional
 
 import numpy as np
 
-from anorag_hip import METRIC_IP, METRIC_L2, FlatIndex
+from anorag_hip import METRIC_IP, METRIC_L2, FlatIndex, IVFIndex
 from anorag_hip._lib import OPT_ADD_RAW
 from anorag_hip.compat import FileUtils, config, default_tmp, hip_available, logger
 
 _SUPPORTED = ("Flat", "IVFFlat", "IVFPQ", "HNSW", "LSH")
 _MAGIC = b"ANRFLAT1"
+_IVF_MAGIC = b"ANRIVF01"
+_IVF_TYPES = ("IVFFlat", "IVFPQ")
+_IVF_NITER = 10    # faiss's IVF coarse-quantiser training (Level1Quantizer sets cp.niter = 10)
+_IVF_SEED = 1234   # faiss's ClusteringParameters default
+
+
+def write_ivf_trailer(f, centroids: np.ndarray) -> None:
+    """The optional trailer an IVF index appends after the rows of its file: magic, int32 nlist, int32 dim, then the
+    centroids as little-endian float32 [nlist, dim]."""
+    c = np.ascontiguousarray(centroids, dtype="<f4")
+    f.write(_IVF_MAGIC)
+    f.write(struct.pack("<ii", int(c.shape[0]), int(c.shape[1])))
+    f.write(c.tobytes())
+
+
+def read_ivf_trailer(f, dim: int) -> Optional[np.ndarray]:
+    """The centroids of the trailer at the file position, or None when the file ends there (an exact index)."""
+    magic = f.read(len(_IVF_MAGIC))
+    if not magic:
+        return None
+    if magic != _IVF_MAGIC:
+        raise ValueError("unknown data after the rows of the index file")
+    nlist, d = struct.unpack("<ii", f.read(8))
+    if d != dim or nlist <= 0:
+        raise ValueError(f"IVF trailer: {nlist} centroids of dim {d} for an index of dim {dim}")
+    c = np.frombuffer(f.read(4 * nlist * d), dtype="<f4")
+    if c.size != nlist * d:
+        raise ValueError("IVF trailer: truncated centroids")
+    return c.reshape(nlist, d).astype(np.float32)
 
 try:  # C shaping of the (scores, indices) arrays into the reference's list of dicts (csrc/pyshape.c)
     from anorag_hip import _pyshape
@@ -64,6 +97,7 @@ class VectorIndex:
         self.is_trained = False
         self.total_vectors = 0
         self._ids: Optional[np.ndarray] = None  # caller-supplied ids (add_with_ids semantics), else sequential
+        self._ivf_live: Optional[np.ndarray] = None  # IVF: which insertion numbers are still in the index
 
         self.index_dir = config.get("storage.vector_index_path")
         if not self.index_dir:
@@ -79,12 +113,26 @@ class VectorIndex:
         if isinstance(devs, int):
             devs = list(range(devs))
         self.devices = [int(v) for v in devs] if devs else [self.device]
+        # anorag_hip.ivf (default false): IVFFlat / IVFPQ become a real IVF-Flat index (anorag_hip.IVFIndex)
+        self.use_ivf = bool(config.get("anorag_hip.ivf", False))
+        if self.use_ivf and len(self.devices) > 1:
+            logger.warning("anorag_hip.ivf is not supported on a sharded index (anorag_hip.devices): staying exact")
+            self.use_ivf = False
         logger.info(f"VectorIndex initialized: dim={self.embedding_dim}, type={self.index_type}, gpu={self.use_gpu}")
 
     # ------------------------------------------------------------------------------------------
     def _cosine(self) -> bool:
         # anything that is not 'cosine' means L2 (reference vector_index.py:69-74)
         return self.similarity_metric == "cosine"
+
+    def _ivf(self) -> bool:
+        return isinstance(self.index, IVFIndex)
+
+    def _new_ivf_index(self, dim: int, metric: int, normalize: bool, nlist: int):
+        # inner product: spherical k-means, as faiss's IndexIVF trains an inner-product quantiser (cp.spherical)
+        idx = IVFIndex(dim, int(nlist), metric, normalize=normalize, device=self.devices[0], spherical=metric == METRIC_IP)
+        idx.nprobe = int(self.nprobe)
+        return idx
 
     def _new_index(self, dim: int, metric: int, normalize: bool):
         if len(self.devices) > 1:
@@ -108,13 +156,18 @@ class VectorIndex:
                 raise ValueError(f"Unsupported index type: {index_type}")
             if self.index is not None:
                 self.index.close()
-            self.index = self._new_index(int(self.embedding_dim), METRIC_IP if self._cosine() else METRIC_L2,
-                                         self._cosine())
+            metric = METRIC_IP if self._cosine() else METRIC_L2
+            if self.use_ivf and index_type in _IVF_TYPES:
+                self.index = self._new_ivf_index(int(self.embedding_dim), metric, self._cosine(), int(self.nlist))
+            else:
+                self.index = self._new_index(int(self.embedding_dim), metric, self._cosine())
             self._ids = None
+            self._ivf_live = None
             if index_type in ("Flat", "HNSW", "LSH"):
                 self.is_trained = True
             self.index_type = index_type
-            logger.info(f"Index created successfully: {index_type} (exact scan on HIP device(s) {self.devices})")
+            how = "IVF-Flat" if self._ivf() else "exact scan"
+            logger.info(f"Index created successfully: {index_type} ({how} on HIP device(s) {self.devices})")
             return True
         except Exception as e:
             logger.error(f"Failed to create index: {e}")
@@ -135,8 +188,10 @@ class VectorIndex:
                 if not self.create_index(self.index_type):
                     self.nlist = old
                     return False
-            self._preprocess_vectors(training_vectors)  # same validation the reference's train performs
-            self.is_trained = True  # an exact scan has nothing to learn
+            v = self._preprocess_vectors(training_vectors)  # same validation the reference's train performs
+            if self._ivf():
+                self.index.train(v, niter=_IVF_NITER, seed=_IVF_SEED)
+            self.is_trained = True  # (an exact scan has nothing to learn)
             return True
         except Exception as e:
             logger.error(f"Failed to train index: {e}")
@@ -153,6 +208,14 @@ class VectorIndex:
             v = np.asarray(vectors)
             if v.ndim != 2:
                 raise ValueError("vectors must be 2-D")  # the reference fails in norm(axis=1) here
+            if self._ivf():
+                if ids is not None and len(np.asarray(ids).reshape(-1)) != len(v):
+                    raise ValueError("ids length mismatch")
+                self.index.add(v)
+                self._ivf_add_ids(len(v), ids)  # only once the device holds the rows
+                self.total_vectors += len(vectors)
+                logger.info(f"Added {len(vectors)} vectors to index, total: {self.total_vectors}")
+                return True
             before = self.index.ntotal
             self.index.add(v)  # cast / contiguity / cosine normalisation happen on the device
             if ids is not None and self.index_type not in ("Flat", "HNSW", "LSH"):
@@ -172,14 +235,40 @@ class VectorIndex:
             logger.error(f"Failed to add vectors to index: {e}")
             return False
 
+    def _ivf_add_ids(self, n: int, ids: Optional[np.ndarray]) -> None:
+        """IVF: self._ids maps every insertion number the device returns (removed rows included) to the caller's id"""
+        first = 0 if self._ids is None else len(self._ids)
+        new = np.arange(first, first + n, dtype=np.int64)
+        if ids is not None:
+            ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+            if len(ids) != n:
+                raise ValueError("ids length mismatch")
+            new = ids
+        self._ids = new if self._ids is None else np.concatenate([self._ids, new])
+        live = np.ones(n, dtype=bool)
+        self._ivf_live = live if self._ivf_live is None or len(self._ids) == n else np.concatenate([self._ivf_live, live])
+
     def add_vectors_device(self, dev_vectors, ids: Optional[np.ndarray] = None) -> bool:
         """EXTENSION: ``add_vectors`` for embeddings that already sit in device memory (an
         ``anorag_hip.fusion.DeviceArray`` [n, dim] float32 on the index's device, e.g. from
         ``EmbeddingManager.encode_texts_device``): the rows go from the encoder to the index without touching the host.
         Single-device index with sequential ids only; returns False otherwise (the caller then uses ``add_vectors``)."""
-        if self.index is None or not isinstance(self.index, FlatIndex):
+        if self.index is None or not isinstance(self.index, (FlatIndex, IVFIndex)):
             return False
         n = int(dev_vectors.nq)
+        if self._ivf():
+            # an untrained IVF index needs the rows on the host for k-means: the caller then uses add_vectors
+            if not self.index.is_trained or dev_vectors.n != self.index.d or dev_vectors.dtype != np.float32 \
+                    or dev_vectors.device != self.index.device:
+                return False
+            try:
+                self.index.add_device(dev_vectors.ptr, n)
+                self._ivf_add_ids(n, ids)
+                self.total_vectors += n
+                return True
+            except Exception as e:
+                logger.error(f"Failed to add vectors to index: {e}")
+                return False
         if dev_vectors.n != self.index.d or dev_vectors.dtype != np.float32 or dev_vectors.device != self.index.device:
             return False
         if ids is not None and not np.array_equal(np.asarray(ids).reshape(-1),
@@ -203,11 +292,16 @@ class VectorIndex:
     def search_device(self, dev_queries, top_k: int = 10) -> List[Dict[str, Any]]:
         """EXTENSION: ``search`` for query embeddings in device memory (``DeviceArray`` [nq, dim] float32); same return
         value as ``search``.  Raises when the index cannot take device queries (the caller falls back)."""
-        if not isinstance(self.index, FlatIndex) or dev_queries.device != self.index.device or dev_queries.n != self.index.d:
+        if not isinstance(self.index, (FlatIndex, IVFIndex)) or dev_queries.device != self.index.device \
+                or dev_queries.n != self.index.d:
             raise ValueError("device queries need a single-device index on the same device")
         if self.total_vectors == 0:
             return []
-        scores, indices = self.index.search_device_queries(dev_queries.ptr, dev_queries.nq, int(top_k))
+        if self._ivf():
+            scores, indices = self.index.search_device_queries(dev_queries.ptr, dev_queries.nq, int(top_k),
+                                                               int(self.nprobe))
+        else:
+            scores, indices = self.index.search_device_queries(dev_queries.ptr, dev_queries.nq, int(top_k))
         if self._ids is not None:
             indices = np.where(indices >= 0, self._ids[np.clip(indices, 0, len(self._ids) - 1)], -1)
         results = _shape_hits(np.ascontiguousarray(indices, dtype=np.int64),
@@ -225,7 +319,10 @@ class VectorIndex:
             q = np.asarray(query_vectors)
             if q.ndim != 2:
                 raise ValueError("query_vectors must be 2-D")
-            scores, indices = self.index.search(q, int(top_k))
+            if self._ivf():
+                scores, indices = self.index.search(q, int(top_k), int(self.nprobe))
+            else:
+                scores, indices = self.index.search(q, int(top_k))
             if self._ids is not None:
                 indices = np.where(indices >= 0, self._ids[np.clip(indices, 0, len(self._ids) - 1)], -1)
             results = _shape_hits(np.ascontiguousarray(indices, dtype=np.int64),
@@ -261,17 +358,29 @@ class VectorIndex:
             filename = filename or f"index_{self.index_type}_{self.embedding_dim}d.faiss"
             filepath = os.path.join(self.index_dir, filename)
             n = self.index.ntotal
+            ivf = self._ivf()
+            if ivf:
+                # the alive rows in insertion order, with the caller's ids when they are not 0..n-1
+                alive = self._ivf_alive()
+                ids_out = self._ids[alive] if self._ids is not None else None
+                if ids_out is not None and np.array_equal(ids_out, np.arange(n, dtype=np.int64)):
+                    ids_out = None
+            else:
+                ids_out = self._ids
             with open(filepath, "wb") as f:
                 f.write(_MAGIC)
                 f.write(struct.pack("<iiiq", int(self.embedding_dim), int(self.index.metric),
                                     int(self.index.normalize), int(n)))
-                has_ids = self._ids is not None
+                has_ids = ids_out is not None
                 f.write(struct.pack("<i", 1 if has_ids else 0))
                 if has_ids:
-                    self._ids.astype("<i8").tofile(f)
+                    ids_out.astype("<i8").tofile(f)
                 step = 1 << 16
                 for s in range(0, n, step):
-                    self.index.reconstruct_n(s, min(step, n - s)).astype("<f4").tofile(f)
+                    rows = self.index.reconstruct(alive[s:s + step]) if ivf else self.index.reconstruct_n(s, min(step, n - s))
+                    rows.astype("<f4").tofile(f)
+                if ivf:
+                    write_ivf_trailer(f, self.index.centroids)
             FileUtils.write_json(self._metadata(), filepath.replace(".faiss", "_metadata.json"))
             logger.info(f"Index saved to {filepath}")
             return filepath
@@ -291,18 +400,36 @@ class VectorIndex:
                 dim, metric, normalize, n = struct.unpack("<iiiq", f.read(20))
                 (has_ids,) = struct.unpack("<i", f.read(4))
                 ids = np.fromfile(f, dtype="<i8", count=n) if has_ids else None
+                rows_at = f.tell()
+                cent = None
+                if self.use_ivf:
+                    f.seek(rows_at + 4 * n * dim)
+                    cent = read_ivf_trailer(f, dim)
+                    f.seek(rows_at)
                 if self.index is not None:
                     self.index.close()
-                self.index = self._new_index(dim, metric, bool(normalize))
-                self.index.reserve(n)
-                self.index.set_option(OPT_ADD_RAW, 1)  # rows were stored already preprocessed
+                if cent is not None:
+                        # rows were stored preprocessed: the IVF index takes them as they are (it still normalises queries)
+                    self.index = self._new_ivf_index(dim, metric, bool(normalize), len(cent))
+                    self.index.set_centroids(cent)
+                    self.index.set_add_raw(True)
+                else:
+                    self.index = self._new_index(dim, metric, bool(normalize))
+                    self.index.reserve(n)
+                    self.index.set_option(OPT_ADD_RAW, 1)  # rows were stored already preprocessed
                 step = 1 << 16
                 for s in range(0, n, step):
                     m = min(step, n - s)
                     rows = np.fromfile(f, dtype="<f4", count=m * dim).reshape(m, dim)
                     self.index.add(rows)
-                self.index.set_option(OPT_ADD_RAW, 0)
+                if cent is None:
+                    self.index.set_option(OPT_ADD_RAW, 0)
+                else:
+                    self.index.set_add_raw(False)
             self._ids = ids
+            if cent is not None:
+                self._ids = ids if ids is not None else np.arange(n, dtype=np.int64)
+                self._ivf_live = np.ones(n, dtype=bool)
             # (attributes come from the sidecar alone, as in the reference, :337-345: without one the loader keeps its own
             # index_type / embedding_dim / similarity_metric / is_trained and total_vectors stays what it was — pinned by
             # tests/golden/index_persistence_cases.json "load_without_sidecar")
@@ -343,6 +470,14 @@ class VectorIndex:
         try:
             n_requested = len(ids)
             drop = np.unique(np.asarray(ids, dtype=np.int64))
+            if self._ivf():  # faiss IVF remove_ids: the rows go, the centroids and the other rows' ids stay
+                full = self._ids if self._ids is not None else np.arange(self._ivf_count(), dtype=np.int64)
+                gone = np.flatnonzero(np.isin(full, drop) & self._ivf_live)
+                self.index.remove_ids(gone)
+                self._ivf_live[gone] = False
+                self.total_vectors -= n_requested
+                logger.info(f"Removed {n_requested} vectors from index")
+                return True
             n = self.index.ntotal
             cur = self._ids if self._ids is not None else np.arange(n, dtype=np.int64)
             keep = ~np.isin(cur, drop)
@@ -368,8 +503,25 @@ class VectorIndex:
             logger.error(f"Failed to remove vectors: {e}")
             return False
 
+    def _ivf_count(self) -> int:
+        """rows ever added to the IVF index (its insertion numbers are 0..this-1)"""
+        return 0 if self._ids is None else len(self._ids)
+
+    def _ivf_alive(self) -> np.ndarray:
+        """insertion numbers of the rows still in the IVF index, ascending"""
+        if self._ivf_live is None:
+            return np.zeros(0, dtype=np.int64)
+        return np.flatnonzero(self._ivf_live).astype(np.int64)
+
     def reset_index(self):
-        if self.index is not None:
+        if self._ivf():  # a fresh IVF index with the same centroids: insertion numbers start again at 0
+            old = self.index
+            self.index = self._new_ivf_index(old.d, old.metric, old.normalize, old.nlist)
+            if old.is_trained:
+                self.index.set_centroids(old.centroids)
+            old.close()
+            self._ivf_live = None
+        elif self.index is not None:
             self.index.reset()
         self._ids = None
         self.total_vectors = 0
@@ -378,8 +530,9 @@ class VectorIndex:
 
     def optimize_search_params(self, query_vectors: np.ndarray, ground_truth_indices: np.ndarray,
                                target_recall: float = 0.9) -> Dict[str, Any]:
-        """nprobe sweep of the reference (vector_index.py:428-470); the scan is exact, so every nprobe
-        yields the same recall and the first tried value is kept."""
+        """nprobe sweep of the reference (vector_index.py:428-470).  An IVF index (anorag_hip.ivf) searches with each
+        nprobe and keeps the best; the exact scan yields the same recall for every nprobe, so there the first tried
+        value is kept."""
         if self.index_type not in ("IVFFlat", "IVFPQ"):
             logger.warning("Search parameter optimization only supported for IVF indices")
             return {}
@@ -387,6 +540,8 @@ class VectorIndex:
         for nprobe in (1, 5, 10, 20, 50, 100):
             if nprobe > self.nlist:
                 break
+            if self._ivf():
+                self.nprobe = nprobe  # an IVF index searches the nprobe nearest lists
             results = self.search(query_vectors, top_k=len(ground_truth_indices[0]))
             # (ONE query: search returns a flat list and _calculate_recall then indexes a str — a TypeError in the reference
             # too, vector_index.py:448-451 / :484; kept, it is pinned by tests/golden/index_persistence_cases.json)

@@ -411,6 +411,53 @@ int anr_bm25_sparse_dev(anr_bm25 *h, int64_t nq, const int64_t *q_indptr, const 
 int anr_bm25_nonzero(anr_bm25 *h, int64_t nq, const int64_t *q_indptr, const int32_t *q_terms, int32_t normalize,
                      int32_t cap, int32_t *out_docs, double *out_scores, int32_t *out_count);
 
+/* ------------------------------------------------------------------------------------------------
+ * IVF-Flat index (opt-in; replaces faiss.IndexIVFFlat where vector_index.py:81-95 builds one, :109-166 trains it and
+ * :428-470 sweeps nprobe).  Separate from anr_index: nothing of the exact index changes.  Rows are assigned to the
+ * nearest of nlist centroids and kept list by list; a search scores the nprobe lists nearest to each query.  Results
+ * are the exact top-k of the probed lists' float32 rows (float64 re-score, ties by ascending id), padded with id -1 and
+ * -FLT_MAX (IP) / +FLT_MAX (L2) when the probed lists hold fewer than k rows.  Ids are global insertion numbers and
+ * survive anr_ivf_remove (faiss IVF semantics); they are never reused.  Limits: dim even and <= 2048, nlist <= 8192,
+ * k <= 1024, fewer than 2^31 - 32 * nlist rows ever added.  Rows are kept twice in float32 and once in f16, and removed
+ * rows keep their float32 copy until the handle is destroyed.  Training, list layout and the certificate are described at the top of csrc/ivf.hip.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct anr_ivf anr_ivf;
+
+int anr_ivf_create(int32_t dim, int32_t metric, int32_t normalize, int32_t nlist, int32_t device, anr_ivf **out);
+int anr_ivf_destroy(anr_ivf *h);
+/* Lloyd's k-means on the device: at most 256 * nlist of the n rows (chosen by seed), initial centroids nlist distinct
+ * rows chosen by seed, niter iterations; an empty list takes half of the largest one.  Deterministic: the same rows and
+ * seed give bit-identical centroids.  Rows already in the index are re-assigned. */
+int anr_ivf_train(anr_ivf *h, const float *x_host, int64_t n, int32_t niter, int64_t seed);
+/* niter Lloyd iterations over all n rows, starting from the current centroids (anr_ivf_set_centroids) */
+int anr_ivf_train_from_centroids(anr_ivf *h, const float *x_host, int64_t n, int32_t niter);
+/* nlist x dim float32 centroids in / out (save and load; set re-assigns the rows already in the index) */
+int anr_ivf_set_centroids(anr_ivf *h, const float *c_host);
+int anr_ivf_get_centroids(anr_ivf *h, float *c_host);
+int anr_ivf_is_trained(const anr_ivf *h);
+/* append n rows (ids continue from the number of rows ever added); needs centroids */
+int anr_ivf_add(anr_ivf *h, const float *x_host, int64_t n);
+int anr_ivf_add_dev(anr_ivf *h, const float *x_dev, int64_t n);
+/* raw != 0: later adds store rows as given (already normalised: reloading a saved index); queries are still normalised */
+int anr_ivf_set_add_raw(anr_ivf *h, int32_t raw);
+/* nq queries, the nprobe nearest lists each (nprobe > nlist means nlist): D[nq*k], I[nq*k] on the host */
+int anr_ivf_search(anr_ivf *h, const float *q_host, int64_t nq, int32_t k, int32_t nprobe, float *D, int64_t *I);
+int anr_ivf_search_devq(anr_ivf *h, const float *q_dev, int64_t nq, int32_t k, int32_t nprobe, float *D, int64_t *I);
+/* rows in the index (removed ones excluded) */
+int64_t anr_ivf_ntotal(const anr_ivf *h);
+/* rows per list, nlist entries */
+int anr_ivf_list_sizes(anr_ivf *h, int64_t *sizes);
+/* the stored (preprocessed) float32 rows of n global ids; ANR_EINVAL for an id not in the index */
+int anr_ivf_reconstruct(anr_ivf *h, const int64_t *ids, int64_t n, float *out_host);
+/* drop the rows with these ids (unknown ids are ignored); the others keep their ids, the centroids stay */
+int anr_ivf_remove(anr_ivf *h, const int64_t *ids, int64_t n, int64_t *n_removed);
+/* 1: spherical k-means — centroids are normalised after every update of anr_ivf_train* (default 0) */
+int anr_ivf_set_spherical(anr_ivf *h, int32_t on);
+/* the list each of n global ids is assigned to; ANR_EINVAL for an id not in the index */
+int anr_ivf_assignments(anr_ivf *h, const int64_t *ids, int64_t n, int32_t *lists);
+/* of the last search: queries, and queries whose certificate failed and that were re-scored exactly over their probed rows */
+int anr_ivf_last_search_stats(anr_ivf *h, int64_t *n_queries, int64_t *n_exact_rescan);
+
 #ifdef __cplusplus
 }
 #endif
