@@ -207,6 +207,14 @@ SIGNATURES = {
     "anr_ivf_set_spherical": (C.c_int, [C.c_void_p, C.c_int32]),
     "anr_ivf_assignments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "anr_ivf_last_search_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "anr_ivf_memory": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "anr_ivf_create_pq": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                    C.POINTER(C.c_void_p)]),
+    "anr_ivf_get_codebooks": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "anr_ivf_set_codebooks": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "anr_ivf_pq_train_from_codebooks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
+    "anr_ivf_codes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "anr_ivf_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
 }
 
 _lib = None

@@ -3,7 +3,9 @@
 ``IVFIndex`` is what the drop-in ``vector_store.VectorIndex`` holds for ``index_type`` IVFFlat / IVFPQ when the config
 key ``anorag_hip.ivf`` is true (reference vector_store/vector_index.py:81-95 builds a ``faiss.IndexIVFFlat`` there): the
 ``train`` / ``add`` / ``search`` / ``remove_ids`` surface of faiss's IVF indexes, with ``nprobe`` passed per search.
-Results are the exact top-k of the probed lists (see include/anorag.h).
+Results are the exact top-k of the probed lists (see include/anorag.h).  With ``pq_m`` the handle is an IVF-PQ index
+(faiss's ``IndexIVFPQ(quantizer, d, nlist, pq_m, 8)``): rows are stored as ``pq_m`` one-byte codes of their residuals and
+a search returns the ADC top-k of the probed lists.
 """
 from __future__ import annotations
 
@@ -17,10 +19,10 @@ from .flat_index import _f32_matrix, _settle_interpreter_heap
 
 
 class IVFIndex:
-    """IVF-Flat inner-product / squared-L2 index resident on one MI355X."""
+    """IVF-Flat (or, with ``pq_m``, IVF-PQ) inner-product / squared-L2 index resident on one MI355X."""
 
     def __init__(self, d: int, nlist: int, metric: int = METRIC_IP, normalize: bool = False, device: int = 0,
-                 spherical: bool = False):
+                 spherical: bool = False, pq_m: int = None):
         self._lib = _lib.load()
         _settle_interpreter_heap()
         self.d = int(d)
@@ -29,9 +31,15 @@ class IVFIndex:
         self.normalize = bool(normalize)
         self.device = int(device)
         self.nprobe = 1
+        self.pq_m = None if pq_m is None else int(pq_m)
         h = C.c_void_p()
-        _lib.check(self._lib.anr_ivf_create(self.d, self.metric, int(self.normalize), self.nlist, self.device,
-                                            C.byref(h)), "anr_ivf_create")
+        self._h = None
+        if self.pq_m is None:
+            _lib.check(self._lib.anr_ivf_create(self.d, self.metric, int(self.normalize), self.nlist, self.device,
+                                                C.byref(h)), "anr_ivf_create")
+        else:
+            _lib.check(self._lib.anr_ivf_create_pq(self.d, self.metric, int(self.normalize), self.nlist, self.pq_m, 8,
+                                                   self.device, C.byref(h)), "anr_ivf_create_pq")
         self._h = h
         if spherical:
             self.set_spherical(True)
@@ -84,6 +92,51 @@ class IVFIndex:
         if c.shape[0] != self.nlist:
             raise ValueError(f"set_centroids: expected {self.nlist} rows, got {c.shape[0]}")
         _lib.check(self._lib.anr_ivf_set_centroids(self._h, c.ctypes.data), "anr_ivf_set_centroids")
+
+    # ---- IVF-PQ (pq_m given) ----
+    @property
+    def codebooks(self) -> np.ndarray:
+        """[pq_m, 256, d / pq_m] float32"""
+        out = np.empty((self.pq_m or 0, 256, self.d // (self.pq_m or 1)), dtype=np.float32)
+        _lib.check(self._lib.anr_ivf_get_codebooks(self._h, out.ctypes.data), "anr_ivf_get_codebooks")
+        return out
+
+    def set_codebooks(self, cb) -> None:
+        """[pq_m, 256, d / pq_m] float32; rows already in the index are re-encoded"""
+        shape = (self.pq_m or 0, 256, self.d // (self.pq_m or 1))
+        cb = np.ascontiguousarray(cb, dtype=np.float32)
+        if cb.shape != shape:
+            raise ValueError(f"set_codebooks: expected shape {shape}, got {cb.shape}")
+        _lib.check(self._lib.anr_ivf_set_codebooks(self._h, cb.ctypes.data), "anr_ivf_set_codebooks")
+
+    def pq_train_from(self, x, niter: int) -> None:
+        """``niter`` Lloyd iterations of every sub-space over the residuals of all rows of ``x``, from the current
+        codebooks"""
+        x = _f32_matrix(x, self.d, "pq_train_from")
+        _lib.check(self._lib.anr_ivf_pq_train_from_codebooks(self._h, x.ctypes.data, x.shape[0], int(niter)),
+                   "anr_ivf_pq_train_from_codebooks")
+
+    def codes(self, ids):
+        """(lists int32 [n], codes uint8 [n, pq_m]) of the given global ids"""
+        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
+        lists = np.empty((len(ids),), dtype=np.int32)
+        codes = np.empty((len(ids), self.pq_m or 0), dtype=np.uint8)
+        _lib.check(self._lib.anr_ivf_codes(self._h, ids.ctypes.data, len(ids), lists.ctypes.data, codes.ctypes.data),
+                   "anr_ivf_codes")
+        return lists, codes
+
+    def decode(self, ids) -> np.ndarray:
+        """c_list + the codebook entries of each id's codes (what an ADC key scores)"""
+        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
+        out = np.empty((len(ids), self.d), dtype=np.float32)
+        _lib.check(self._lib.anr_ivf_decode(self._h, ids.ctypes.data, len(ids), out.ctypes.data), "anr_ivf_decode")
+        return out
+
+    def memory(self) -> dict:
+        """{'device_bytes', 'host_bytes'}: the persistent storage of the index (search scratch excluded)"""
+        a, b = C.c_int64(0), C.c_int64(0)
+        _lib.check(self._lib.anr_ivf_memory(self._h, C.byref(a), C.byref(b)), "anr_ivf_memory")
+        return {"device_bytes": int(a.value), "host_bytes": int(b.value)}
 
     def add(self, x) -> None:
         x = _f32_matrix(x, self.d, "add")

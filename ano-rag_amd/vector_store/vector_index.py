@@ -9,12 +9,16 @@ Differences a maintainer should know (also in INTEGRATION.md):
     those of ``Flat`` (a superset of what the approximate types would return); ``nlist`` / ``nprobe`` /
     ``is_trained`` keep their bookkeeping semantics — unless the config key ``anorag_hip.ivf`` is true: IVFFlat and
     IVFPQ are then served by ``anorag_hip.IVFIndex`` (IVF-Flat: device k-means with ``nlist`` lists, ``nprobe`` lists
-    scanned per query, the exact top-k of the probed rows; IVFPQ gets IVF-Flat, there is no product quantiser);
-    single device only (with ``anorag_hip.devices`` the index stays exact);
+    scanned per query, the exact top-k of the probed rows).  IVFPQ gets IVF-Flat too, unless ``anorag_hip.ivf_pq`` is
+    also true: it is then a real IVF-PQ index (``IVFIndex(..., pq_m=vector_store.pq_m)``: ``pq_m`` one-byte codes of
+    each row's residual on the device, the ADC top-k of the probed lists, faiss's IVFPQ answer); single device only
+    (with ``anorag_hip.devices`` the index stays exact);
   * ``save_index`` writes this build's own container (header + float32 rows) under the reference's file
     name ``index_{type}_{dim}d.faiss`` with the same ``_metadata.json`` sidecar; a file written by faiss
     cannot be read (``load_index`` returns False); an IVF index appends a trailer (``write_ivf_trailer``) that only
-    a loader with ``anorag_hip.ivf`` on reads;
+    a loader with ``anorag_hip.ivf`` on reads, and an IVF-PQ index a second one with its codebooks
+    (``write_pq_trailer``) that only a loader with ``anorag_hip.ivf_pq`` on reads (the others get IVF-Flat or the
+    exact index from the same file);
   * there is no CPU path: with no HIP device ``create_index`` logs the error and returns False.
 """
 from __future__ import annotations
@@ -35,6 +39,7 @@ _IVF_MAGIC = b"ANRIVF01"
 _IVF_TYPES = ("IVFFlat", "IVFPQ")
 _IVF_NITER = 10    # faiss's IVF coarse-quantiser training (Level1Quantizer sets cp.niter = 10)
 _IVF_SEED = 1234   # faiss's ClusteringParameters default
+_PQ_MAGIC = b"ANRPQ001"
 
 
 def write_ivf_trailer(f, centroids: np.ndarray) -> None:
@@ -60,6 +65,32 @@ def read_ivf_trailer(f, dim: int) -> Optional[np.ndarray]:
     if c.size != nlist * d:
         raise ValueError("IVF trailer: truncated centroids")
     return c.reshape(nlist, d).astype(np.float32)
+
+def write_pq_trailer(f, codebooks: np.ndarray) -> None:
+    """The IVF-PQ trailer, after the IVF one: magic, int32 m, int32 nbits (8), int32 dsub, then the codebooks as
+    little-endian float32 [m, 256, dsub]."""
+    cb = np.ascontiguousarray(codebooks, dtype="<f4")
+    f.write(_PQ_MAGIC)
+    f.write(struct.pack("<iii", int(cb.shape[0]), 8, int(cb.shape[2])))
+    f.write(cb.tobytes())
+
+
+def read_pq_trailer(f, dim: int) -> Optional[np.ndarray]:
+    """The codebooks of the PQ trailer at the file position (right after the IVF trailer's centroids), or None when the
+    file ends there (an IVF-Flat index)."""
+    magic = f.read(len(_PQ_MAGIC))
+    if not magic:
+        return None
+    if magic != _PQ_MAGIC:
+        raise ValueError("unknown data after the IVF trailer of the index file")
+    m, nbits, dsub = struct.unpack("<iii", f.read(12))
+    if nbits != 8 or m <= 0 or dsub <= 0 or m * dsub != dim:
+        raise ValueError(f"PQ trailer: m {m}, nbits {nbits}, dsub {dsub} for an index of dim {dim}")
+    cb = np.frombuffer(f.read(4 * m * 256 * dsub), dtype="<f4")
+    if cb.size != m * 256 * dsub:
+        raise ValueError("PQ trailer: truncated codebooks")
+    return cb.reshape(m, 256, dsub).astype(np.float32)
+
 
 try:  # C shaping of the (scores, indices) arrays into the reference's list of dicts (csrc/pyshape.c)
     from anorag_hip import _pyshape
@@ -118,6 +149,8 @@ class VectorIndex:
         if self.use_ivf and len(self.devices) > 1:
             logger.warning("anorag_hip.ivf is not supported on a sharded index (anorag_hip.devices): staying exact")
             self.use_ivf = False
+        # anorag_hip.ivf_pq (default false; only with anorag_hip.ivf): IVFPQ becomes a real IVF-PQ index with m = pq_m
+        self.use_ivf_pq = self.use_ivf and bool(config.get("anorag_hip.ivf_pq", False))
         logger.info(f"VectorIndex initialized: dim={self.embedding_dim}, type={self.index_type}, gpu={self.use_gpu}")
 
     # ------------------------------------------------------------------------------------------
@@ -128,9 +161,11 @@ class VectorIndex:
     def _ivf(self) -> bool:
         return isinstance(self.index, IVFIndex)
 
-    def _new_ivf_index(self, dim: int, metric: int, normalize: bool, nlist: int):
-        # inner product: spherical k-means, as faiss's IndexIVF trains an inner-product quantiser (cp.spherical)
-        idx = IVFIndex(dim, int(nlist), metric, normalize=normalize, device=self.devices[0], spherical=metric == METRIC_IP)
+    def _new_ivf_index(self, dim: int, metric: int, normalize: bool, nlist: int, pq_m: Optional[int] = None):
+        # inner product: spherical k-means, as faiss's IndexIVF trains an inner-product quantiser (cp.spherical); the
+        # PQ's own k-means is always L2
+        idx = IVFIndex(dim, int(nlist), metric, normalize=normalize, device=self.devices[0], spherical=metric == METRIC_IP,
+                       pq_m=pq_m)
         idx.nprobe = int(self.nprobe)
         return idx
 
@@ -158,7 +193,8 @@ class VectorIndex:
                 self.index.close()
             metric = METRIC_IP if self._cosine() else METRIC_L2
             if self.use_ivf and index_type in _IVF_TYPES:
-                self.index = self._new_ivf_index(int(self.embedding_dim), metric, self._cosine(), int(self.nlist))
+                pq_m = int(self.m) if index_type == "IVFPQ" and self.use_ivf_pq else None
+                self.index = self._new_ivf_index(int(self.embedding_dim), metric, self._cosine(), int(self.nlist), pq_m)
             else:
                 self.index = self._new_index(int(self.embedding_dim), metric, self._cosine())
             self._ids = None
@@ -166,7 +202,7 @@ class VectorIndex:
             if index_type in ("Flat", "HNSW", "LSH"):
                 self.is_trained = True
             self.index_type = index_type
-            how = "IVF-Flat" if self._ivf() else "exact scan"
+            how = ("IVF-PQ" if self.index.pq_m else "IVF-Flat") if self._ivf() else "exact scan"
             logger.info(f"Index created successfully: {index_type} ({how} on HIP device(s) {self.devices})")
             return True
         except Exception as e:
@@ -381,6 +417,8 @@ class VectorIndex:
                     rows.astype("<f4").tofile(f)
                 if ivf:
                     write_ivf_trailer(f, self.index.centroids)
+                    if self.index.pq_m:
+                        write_pq_trailer(f, self.index.codebooks)
             FileUtils.write_json(self._metadata(), filepath.replace(".faiss", "_metadata.json"))
             logger.info(f"Index saved to {filepath}")
             return filepath
@@ -401,17 +439,22 @@ class VectorIndex:
                 (has_ids,) = struct.unpack("<i", f.read(4))
                 ids = np.fromfile(f, dtype="<i8", count=n) if has_ids else None
                 rows_at = f.tell()
-                cent = None
+                cent = cb = None
                 if self.use_ivf:
                     f.seek(rows_at + 4 * n * dim)
                     cent = read_ivf_trailer(f, dim)
+                    if cent is not None and self.use_ivf_pq:
+                        cb = read_pq_trailer(f, dim)
                     f.seek(rows_at)
                 if self.index is not None:
                     self.index.close()
                 if cent is not None:
                         # rows were stored preprocessed: the IVF index takes them as they are (it still normalises queries)
-                    self.index = self._new_ivf_index(dim, metric, bool(normalize), len(cent))
+                    self.index = self._new_ivf_index(dim, metric, bool(normalize), len(cent),
+                                                     None if cb is None else cb.shape[0])
                     self.index.set_centroids(cent)
+                    if cb is not None:  # the rows below are re-encoded with these codebooks: the saved codes again
+                        self.index.set_codebooks(cb)
                     self.index.set_add_raw(True)
                 else:
                     self.index = self._new_index(dim, metric, bool(normalize))
@@ -516,9 +559,11 @@ class VectorIndex:
     def reset_index(self):
         if self._ivf():  # a fresh IVF index with the same centroids: insertion numbers start again at 0
             old = self.index
-            self.index = self._new_ivf_index(old.d, old.metric, old.normalize, old.nlist)
+            self.index = self._new_ivf_index(old.d, old.metric, old.normalize, old.nlist, old.pq_m)
             if old.is_trained:
                 self.index.set_centroids(old.centroids)
+                if old.pq_m:
+                    self.index.set_codebooks(old.codebooks)
             old.close()
             self._ivf_live = None
         elif self.index is not None:

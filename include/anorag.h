@@ -457,6 +457,39 @@ int anr_ivf_set_spherical(anr_ivf *h, int32_t on);
 int anr_ivf_assignments(anr_ivf *h, const int64_t *ids, int64_t n, int32_t *lists);
 /* of the last search: queries, and queries whose certificate failed and that were re-scored exactly over their probed rows */
 int anr_ivf_last_search_stats(anr_ivf *h, int64_t *n_queries, int64_t *n_exact_rescan);
+/* device and host bytes of the handle's persistent storage (rows, codes, ids, lists, centroids, codebooks; per-search
+ * and per-add scratch excluded), after the list-ordered copy is brought up to date; either pointer may be NULL */
+int anr_ivf_memory(anr_ivf *h, int64_t *device_bytes, int64_t *host_bytes);
+
+/* ------------------------------------------------------------------------------------------------
+ * IVF-PQ mode of the same handle (opt-in; replaces faiss.IndexIVFPQ(quantizer, d, nlist, m, 8), vector_index.py:88-92).
+ * Every anr_ivf_* entry above works on it; what changes:
+ *  - the coarse quantiser is IVF-Flat's.  A row is stored as its list and m one-byte codes: code j is the nearest
+ *    (float64 argmin of |r_j - cb_j[c]|^2, ties to the lower code) of the 256 entries of codebook j to sub-vector j of
+ *    the residual r = x - c_list (float32).  The device holds only the codes (list-ordered, m bytes per row in 64-row
+ *    tiles), the ids, the list offsets, the centroids and the codebooks; the preprocessed float32 rows stay in host
+ *    memory in insertion order (reconstruct, saving, re-encoding after a change of centroids or codebooks).
+ *  - anr_ivf_train trains the coarse quantiser as for IVF-Flat, then the codebooks: the first min(n, 65536) rows of the
+ *    same seeded permutation, their residuals, one L2 k-means of 25 iterations per sub-space (never spherical),
+ *    starting from the sub-vectors of the first 256 of those rows; means and the empty-entry rule are the coarse
+ *    quantiser's, so the same rows and seed give bit-identical codebooks.  Fewer than 256 rows: ANR_EINVAL.
+ *  - anr_ivf_search returns the ADC top-k of the probed lists (faiss's IVFPQ answer; no re-rank against the rows), by
+ *    (key desc, id asc).  IP key q.c_list + sum_j q_j.cb_j[code_j]; L2 distance sum_j |(q - c_list)_j - cb_j[code_j]|^2;
+ *    the sums are float32.  D is the key (IP) or the distance (L2).  n_exact_rescan is always 0.
+ * Limits: nbits == 8, m <= 128, dim % m == 0 with dim / m even, and the IVF-Flat limits.  Violations: ANR_EINVAL.
+ * ---------------------------------------------------------------------------------------------- */
+int anr_ivf_create_pq(int32_t dim, int32_t metric, int32_t normalize, int32_t nlist, int32_t m, int32_t nbits,
+                      int32_t device, anr_ivf **out);
+/* m x 256 x (dim / m) float32 codebooks in / out; set re-encodes the rows already in the index */
+int anr_ivf_get_codebooks(anr_ivf *h, float *cb_host);
+int anr_ivf_set_codebooks(anr_ivf *h, const float *cb_host);
+/* niter Lloyd iterations of every sub-space over the residuals of all n rows, starting from the current codebooks
+ * (needs centroids and codebooks); the rows in the index are re-encoded */
+int anr_ivf_pq_train_from_codebooks(anr_ivf *h, const float *x_host, int64_t n, int32_t niter);
+/* the list and the m code bytes (codes_out[n][m]) of n global ids; ANR_EINVAL for an id not in the index */
+int anr_ivf_codes(anr_ivf *h, const int64_t *ids, int64_t n, int32_t *lists_out, uint8_t *codes_out);
+/* c_list + the codebook entries of each id's codes, float32 (faiss's IVFPQ reconstruct) */
+int anr_ivf_decode(anr_ivf *h, const int64_t *ids, int64_t n, float *out_host);
 
 #ifdef __cplusplus
 }
