@@ -668,10 +668,13 @@ struct ScanChunk8 {
   static constexpr int64_t kScaleChunkBytes = CH;  // CH / 2 scales of 2 bytes
   // the lane's scales of a tile's first chunk minus its codes of that chunk (both in the tile): kb * 512 + row * kb - lane * 16
   static __device__ __forceinline__ int kScaleOffset(int kb, int lane) { return kb * 512 + (lane & 31) * kb - lane * 16; }
+  // The scales keep the default cache policy even in a streaming pass: a tile's scale block (kb * 32 bytes, 12 lines of
+  // 128 B at kb 48) is read once per chunk, 8 or 4 bytes per row each time, so every chunk touches all of its lines.  With
+  // the non-temporal hint those lines left the L2 between chunks and came from HBM again: 1.17 x the algorithmic bytes
+  // per 10 M-row pass, against 1.00 x with the lines kept (DESIGN.md §4 "Round 8").
   template <bool STREAM>
   static __device__ __forceinline__ su load_scales(const char *sx) {
-    const su *p = reinterpret_cast<const su *>(sx);
-    return STREAM ? __builtin_nontemporal_load(p) : *p;
+    return *reinterpret_cast<const su *>(sx);
   }
   template <bool STREAM>
   __device__ __forceinline__ void load_code(const char *x, int j) {
