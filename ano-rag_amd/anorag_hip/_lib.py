@@ -58,6 +58,16 @@ class SearchStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class GraphStats(C.Structure):
+    _fields_ = [("builds", C.c_int64), ("last_nq", C.c_int64), ("last_iterations", C.c_int64),
+                ("last_rows_scored", C.c_int64), ("last_capped", C.c_int64), ("graph_bytes", C.c_int64),
+                ("image_bytes", C.c_int64), ("R", C.c_int32), ("build_degree", C.c_int32), ("has_graph", C.c_int32),
+                ("stale", C.c_int32), ("knn_ms", C.c_float), ("prune_ms", C.c_float), ("image_ms", C.c_float)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class FuseSource(C.Structure):
     _fields_ = [("array_dev", C.c_void_p), ("array_len", C.c_int64), ("array_dtype", C.c_int32),
                 ("list_ids", C.c_void_p), ("list_scores", C.c_void_p), ("list_offs", C.c_void_p),
@@ -215,6 +225,16 @@ SIGNATURES = {
     "anr_ivf_pq_train_from_codebooks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
     "anr_ivf_codes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "anr_ivf_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "anr_index_graph_build": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    "anr_index_graph_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                         C.c_void_p]),
+    "anr_index_graph_search_devq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                              C.c_void_p]),
+    "anr_index_graph_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
+    "anr_index_graph_set": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
+    "anr_index_graph_knn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
+    "anr_index_graph_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "anr_index_graph_stats": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "graph.hpp"
 #include "index_kernels.hpp"
 #include "tiny_kernels.hpp"
 
@@ -154,6 +155,7 @@ struct anr_index {
   unsigned long long *tiny_stamps = nullptr;      // developer aid: ANORAG_TINY_STAMPS=1 prints the kernel's phase times
 
   anr_search_stats stats{};
+  anr_graph *graph = nullptr;  // graph index on these rows (graph.hip); adds and resets mark it stale
 };
 
 namespace {
@@ -1482,6 +1484,7 @@ int add_impl(anr_index *h, const float *x_dev, int64_t n, hipStream_t st) {
   h->ntotal += n;
   h->xstat_dirty = true;
   h->x12_no_memory = false;
+  graph_mark_stale(h->graph);
   return ANR_OK;
 }
 
@@ -1585,6 +1588,7 @@ int anr_index_destroy(anr_index *h) {
   dev_free(h->sr_buf);
   dev_free(h->tiny_ticket);
   dev_free(h->tiny_stamps);
+  graph_free(h->graph);
   for (auto &e : h->ev_call)
     if (e) (void)hipEventDestroy(e);
   for (hipStream_t s : {h->bstream[0], h->bstream[1], h->bstream[2], h->stream})
@@ -1654,6 +1658,7 @@ int anr_index_reset(anr_index *h) {
   ANR_HIP(hipStreamSynchronize(nullptr));  // the fills run on the NULL stream; later adds use the handle's own
   h->ntotal = 0;
   h->xstat_dirty = true;
+  graph_mark_stale(h->graph);
   h->f12_suspended = false;
   h->f12_strikes = h->f12_level = h->f12_clean = h->f12_lowered = 0;
   h->f12_hold = 64;
@@ -2126,3 +2131,13 @@ int anr_merge_topk_dev(int32_t device, const float *Dp_dev, const int64_t *Ip_de
 }
 
 }  // extern "C"
+
+namespace anr {
+
+IndexCore index_core(anr_index *h) {
+  return IndexCore{h->x32, h->ntotal, h->dim, h->metric, h->normalize, h->device, h->id_offset, h->stream, &h->mu};
+}
+
+anr_graph *&index_graph(anr_index *h) { return h->graph; }
+
+}  // namespace anr

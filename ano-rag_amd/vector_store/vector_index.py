@@ -19,6 +19,10 @@ Differences a maintainer should know (also in INTEGRATION.md):
     a loader with ``anorag_hip.ivf`` on reads, and an IVF-PQ index a second one with its codebooks
     (``write_pq_trailer``) that only a loader with ``anorag_hip.ivf_pq`` on reads (the others get IVF-Flat or the
     exact index from the same file);
+  * with the config key ``anorag_hip.graph`` true, ``HNSW`` is served by ``anorag_hip.GraphIndex`` (a fixed-degree
+    graph built from the index's own exact kNN lists, searched by a beam of ``ef_search`` = 100 entries; single device
+    only); its file carries the adjacency in a trailer (``write_graph_trailer``) that only a loader with the key on
+    reads;
   * there is no CPU path: with no HIP device ``create_index`` logs the error and returns False.
 """
 from __future__ import annotations
@@ -29,7 +33,7 @@ from typing import Any, Dict, List, Optional
 
 import numpy as np
 
-from anorag_hip import METRIC_IP, METRIC_L2, FlatIndex, IVFIndex
+from anorag_hip import METRIC_IP, METRIC_L2, FlatIndex, GraphIndex, IVFIndex
 from anorag_hip._lib import OPT_ADD_RAW
 from anorag_hip.compat import FileUtils, config, default_tmp, hip_available, logger
 
@@ -40,6 +44,10 @@ _IVF_TYPES = ("IVFFlat", "IVFPQ")
 _IVF_NITER = 10    # faiss's IVF coarse-quantiser training (Level1Quantizer sets cp.niter = 10)
 _IVF_SEED = 1234   # faiss's ClusteringParameters default
 _PQ_MAGIC = b"ANRPQ001"
+_GRAPH_MAGIC = b"ANRGRPH1"
+_GRAPH_R = 64             # faiss HNSW with M = 32 keeps 2 M neighbours on level 0 (vector_index.py:94)
+_GRAPH_BUILD_DEGREE = 128
+_GRAPH_EF_SEARCH = 100    # vector_index.py:99
 
 
 def write_ivf_trailer(f, centroids: np.ndarray) -> None:
@@ -54,7 +62,7 @@ def write_ivf_trailer(f, centroids: np.ndarray) -> None:
 def read_ivf_trailer(f, dim: int) -> Optional[np.ndarray]:
     """The centroids of the trailer at the file position, or None when the file ends there (an exact index)."""
     magic = f.read(len(_IVF_MAGIC))
-    if not magic:
+    if not magic or magic == _GRAPH_MAGIC:  # an exact index, or a graph index's trailer
         return None
     if magic != _IVF_MAGIC:
         raise ValueError("unknown data after the rows of the index file")
@@ -90,6 +98,30 @@ def read_pq_trailer(f, dim: int) -> Optional[np.ndarray]:
     if cb.size != m * 256 * dsub:
         raise ValueError("PQ trailer: truncated codebooks")
     return cb.reshape(m, 256, dsub).astype(np.float32)
+
+
+def write_graph_trailer(f, adj: np.ndarray) -> None:
+    """The trailer a graph index appends after the rows of its file: magic, int64 n, int32 R, then the adjacency as
+    little-endian int32 [n, R] (-1 padded)."""
+    a = np.ascontiguousarray(adj, dtype="<i4")
+    f.write(_GRAPH_MAGIC)
+    f.write(struct.pack("<qi", int(a.shape[0]), int(a.shape[1])))
+    f.write(a.tobytes())
+
+
+def read_graph_trailer(f, n: int) -> Optional[np.ndarray]:
+    """The adjacency of the graph trailer at the file position, or None when there is none (the file ends there, or
+    another trailer follows the rows)."""
+    magic = f.read(len(_GRAPH_MAGIC))
+    if magic != _GRAPH_MAGIC:
+        return None
+    rows, R = struct.unpack("<qi", f.read(12))
+    if rows != n or R <= 0:
+        raise ValueError(f"graph trailer: {rows} rows of degree {R} for an index of {n} rows")
+    a = np.frombuffer(f.read(4 * rows * R), dtype="<i4")
+    if a.size != rows * R:
+        raise ValueError("graph trailer: truncated adjacency")
+    return a.reshape(rows, R).astype(np.int32)
 
 
 try:  # C shaping of the (scores, indices) arrays into the reference's list of dicts (csrc/pyshape.c)
@@ -151,6 +183,11 @@ class VectorIndex:
             self.use_ivf = False
         # anorag_hip.ivf_pq (default false; only with anorag_hip.ivf): IVFPQ becomes a real IVF-PQ index with m = pq_m
         self.use_ivf_pq = self.use_ivf and bool(config.get("anorag_hip.ivf_pq", False))
+        # anorag_hip.graph (default false): HNSW becomes a real graph index (anorag_hip.GraphIndex)
+        self.use_graph = bool(config.get("anorag_hip.graph", False))
+        if self.use_graph and len(self.devices) > 1:
+            logger.warning("anorag_hip.graph is not supported on a sharded index (anorag_hip.devices): staying exact")
+            self.use_graph = False
         logger.info(f"VectorIndex initialized: dim={self.embedding_dim}, type={self.index_type}, gpu={self.use_gpu}")
 
     # ------------------------------------------------------------------------------------------
@@ -169,8 +206,11 @@ class VectorIndex:
         idx.nprobe = int(self.nprobe)
         return idx
 
-    def _new_index(self, dim: int, metric: int, normalize: bool):
-        if len(self.devices) > 1:
+    def _new_index(self, dim: int, metric: int, normalize: bool, graph: bool = False):
+        if graph:  # (the key is off on a sharded index)
+            idx = GraphIndex(dim, metric, normalize=normalize, device=self.devices[0], R=_GRAPH_R,
+                             build_degree=_GRAPH_BUILD_DEGREE, ef_search=_GRAPH_EF_SEARCH)
+        elif len(self.devices) > 1:
             from anorag_hip.sharded import ShardedFlatIndex
             idx = ShardedFlatIndex(dim, metric, normalize=normalize, devices=self.devices)
         else:
@@ -184,6 +224,10 @@ class VectorIndex:
             idx.set_option(OPT_SCAN_BITS, bits)
         return idx
 
+    def _graph_kw(self, graph: bool) -> Dict[str, Any]:
+        # the graph index is asked for only when it is wanted: the exact call stays _new_index(dim, metric, normalize)
+        return {"graph": True} if graph and self.use_graph else {}
+
     def create_index(self, index_type: str = None) -> bool:
         index_type = index_type or self.index_type
         try:
@@ -196,13 +240,15 @@ class VectorIndex:
                 pq_m = int(self.m) if index_type == "IVFPQ" and self.use_ivf_pq else None
                 self.index = self._new_ivf_index(int(self.embedding_dim), metric, self._cosine(), int(self.nlist), pq_m)
             else:
-                self.index = self._new_index(int(self.embedding_dim), metric, self._cosine())
+                self.index = self._new_index(int(self.embedding_dim), metric, self._cosine(),
+                                             **self._graph_kw(index_type == "HNSW"))
             self._ids = None
             self._ivf_live = None
             if index_type in ("Flat", "HNSW", "LSH"):
                 self.is_trained = True
             self.index_type = index_type
-            how = ("IVF-PQ" if self.index.pq_m else "IVF-Flat") if self._ivf() else "exact scan"
+            how = ("IVF-PQ" if self.index.pq_m else "IVF-Flat") if self._ivf() else \
+                ("graph" if isinstance(self.index, GraphIndex) else "exact scan")
             logger.info(f"Index created successfully: {index_type} ({how} on HIP device(s) {self.devices})")
             return True
         except Exception as e:
@@ -415,6 +461,10 @@ class VectorIndex:
                 for s in range(0, n, step):
                     rows = self.index.reconstruct(alive[s:s + step]) if ivf else self.index.reconstruct_n(s, min(step, n - s))
                     rows.astype("<f4").tofile(f)
+                if isinstance(self.index, GraphIndex) and self.index.has_fresh_graph():
+                    # only a graph that exists and matches the rows: saving never runs a build (a loader with the key
+                    # on builds it at its first search, as for a file without the trailer)
+                    write_graph_trailer(f, self.index.adjacency())
                 if ivf:
                     write_ivf_trailer(f, self.index.centroids)
                     if self.index.pq_m:
@@ -439,13 +489,22 @@ class VectorIndex:
                 (has_ids,) = struct.unpack("<i", f.read(4))
                 ids = np.fromfile(f, dtype="<i8", count=n) if has_ids else None
                 rows_at = f.tell()
-                cent = cb = None
+                cent = cb = adj = None
                 if self.use_ivf:
                     f.seek(rows_at + 4 * n * dim)
                     cent = read_ivf_trailer(f, dim)
                     if cent is not None and self.use_ivf_pq:
                         cb = read_pq_trailer(f, dim)
                     f.seek(rows_at)
+                graph = False
+                if self.use_graph:
+                    f.seek(rows_at + 4 * n * dim)
+                    adj = read_graph_trailer(f, n)
+                    f.seek(rows_at)
+                    meta_file = filepath.replace(".faiss", "_metadata.json")
+                    saved_type = FileUtils.read_json(meta_file).get("index_type") if os.path.exists(meta_file) \
+                        else self.index_type
+                    graph = adj is not None or (cent is None and saved_type == "HNSW")
                 if self.index is not None:
                     self.index.close()
                 if cent is not None:
@@ -457,7 +516,7 @@ class VectorIndex:
                         self.index.set_codebooks(cb)
                     self.index.set_add_raw(True)
                 else:
-                    self.index = self._new_index(dim, metric, bool(normalize))
+                    self.index = self._new_index(dim, metric, bool(normalize), **self._graph_kw(graph))
                     self.index.reserve(n)
                     self.index.set_option(OPT_ADD_RAW, 1)  # rows were stored already preprocessed
                 step = 1 << 16
@@ -467,6 +526,8 @@ class VectorIndex:
                     self.index.add(rows)
                 if cent is None:
                     self.index.set_option(OPT_ADD_RAW, 0)
+                    if adj is not None and graph:
+                        self.index.set_adjacency(adj)  # the saved graph: no rebuild
                 else:
                     self.index.set_add_raw(False)
             self._ids = ids
@@ -501,6 +562,8 @@ class VectorIndex:
         if self.index_type in ("IVFFlat", "IVFPQ"):
             stats["nlist"] = self.nlist
             stats["nprobe"] = self.nprobe
+        if isinstance(self.index, GraphIndex):
+            stats["ef_search"] = self.index.ef_search
         return stats
 
     def remove_vectors(self, ids: np.ndarray) -> bool:
@@ -526,7 +589,8 @@ class VectorIndex:
             keep = ~np.isin(cur, drop)
             rows = self.index.reconstruct_n(0, n)[keep] if n else np.zeros((0, self.embedding_dim), np.float32)
             # build the replacement beside the live index and swap only when it is complete
-            fresh = self._new_index(int(self.index.d), self.index.metric, self.index.normalize)
+            fresh = self._new_index(int(self.index.d), self.index.metric, self.index.normalize,
+                                    **self._graph_kw(isinstance(self.index, GraphIndex)))
             try:
                 fresh.set_option(OPT_ADD_RAW, 1)  # the rows are stored already preprocessed
                 if len(rows):

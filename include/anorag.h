@@ -491,6 +491,50 @@ int anr_ivf_codes(anr_ivf *h, const int64_t *ids, int64_t n, int32_t *lists_out,
 /* c_list + the codebook entries of each id's codes, float32 (faiss's IVFPQ reconstruct) */
 int anr_ivf_decode(anr_ivf *h, const int64_t *ids, int64_t n, float *out_host);
 
+/* ------------------------------------------------------------------------------------------------
+ * Graph index on an anr_index handle (opt-in; replaces the faiss.IndexHNSWFlat(d, 32, metric) with efConstruction 200 /
+ * efSearch 100 that vector_index.py:94-99 builds): one level, fixed out-degree R, built from the handle's own exact
+ * kNN lists, searched by a beam of ef entries.  The graph reads the handle's stored float32 rows (no second copy) and
+ * keeps an int8 traversal image (dim rounded up to 16 bytes + 8 bytes per row) and the [n][R] int32 adjacency on the
+ * device.  An add or a reset marks the graph stale: the next graph call that needs it rebuilds it with the same R and
+ * build_degree (counted in builds).  Build, prune rule and search: top of csrc/graph.hip and DESIGN.md §5d.  Graph calls
+ * must not overlap an add or a reset of the same handle from another thread (a build reads the rows in place).
+ * Limits: dim <= 2048, fewer than 2^31 - 1 rows, R even in 2..128, build_degree in 1..255, 1 <= k, ef and
+ * max(k, ef) <= 256.  Violations: ANR_EINVAL; a graph call other than build / set before any graph: ANR_ESTATE.
+ * ---------------------------------------------------------------------------------------------- */
+/* build the graph of the current rows (vector_index.py:94-99): exact top-(build_degree + 1) lists, pruned to R.
+ * keep_knn != 0 keeps the pre-prune lists of this build and its rebuilds for anr_index_graph_knn (n * build_degree int32
+ * of host memory; tests) */
+int anr_index_graph_build(anr_index *h, int32_t R, int32_t build_degree, int32_t keep_knn);
+/* beam search of nq queries (vector_index.py:223 on an HNSW index, efSearch = ef): D / I [nq][k] host buffers, the best
+ * k rows of the beam by float64 re-score from the stored rows, ties by ascending id, padded as anr_index_search */
+int anr_index_graph_search(anr_index *h, const float *q_host, int64_t nq, int32_t k, int32_t ef, float *D, int64_t *I);
+int anr_index_graph_search_devq(anr_index *h, const float *q_dev, int64_t nq, int32_t k, int32_t ef, float *D,
+                                int64_t *I);
+/* the adjacency [n][R] (-1 padded) out / in (persistence, vector_index.py:94-99 save / load).  get rebuilds a stale
+ * graph first, then needs the caller's buffer shape n, R to be the graph's (ANR_EINVAL otherwise); set needs n == ntotal */
+int anr_index_graph_get(anr_index *h, int32_t *adj, int64_t n, int32_t R);
+int anr_index_graph_set(anr_index *h, const int32_t *adj, int64_t n, int32_t R);
+/* the pre-prune kNN lists [n][build_degree] of the last build (tests).  A stale graph is rebuilt first; the buffer
+ * shape n, build_degree must be the current one (ANR_EINVAL otherwise); ANR_ESTATE when the lists were not kept
+ * (built without keep_knn, or the graph came from anr_index_graph_set) */
+int anr_index_graph_knn(anr_index *h, int32_t *lists, int64_t n, int32_t K);
+/* rows of the traversal image decoded to float32, out [n][dim] (tests) */
+int anr_index_graph_image(anr_index *h, const int64_t *ids, int64_t n, float *out);
+typedef struct anr_graph_stats {
+  int64_t builds;            /* graph builds so far (anr_index_graph_build and rebuilds of a stale graph) */
+  int64_t last_nq;           /* queries of the last graph search                                           */
+  int64_t last_iterations;   /* beam iterations (p parents expanded each), summed over those queries        */
+  int64_t last_rows_scored;  /* traversal-image rows scored, summed over those queries                      */
+  int64_t last_capped;       /* queries that stopped at the iteration cap instead of a fully expanded beam  */
+  int64_t graph_bytes;       /* device bytes of the adjacency                                               */
+  int64_t image_bytes;       /* device bytes of the traversal image                                         */
+  int32_t R, build_degree;
+  int32_t has_graph, stale;
+  float knn_ms, prune_ms, image_ms;  /* host wall time of the phases of the last build                   */
+} anr_graph_stats;
+int anr_index_graph_stats(anr_index *h, anr_graph_stats *out);
+
 #ifdef __cplusplus
 }
 #endif
