@@ -1518,9 +1518,12 @@ __global__ __launch_bounds__(1024) void k_post(SelParams p, PostParams pp) {
       const float qn = pp.qstat[q * 4 + 0], qh = pp.qstat[q * 4 + 1], qe = pp.qstat[q * 4 + 2];
       double eps = (double)xerr * qh + (double)xmax * qe + 2.0 * pp.dimp * 5.9604645e-8 * (double)xmax * qn;
       if (pp.metric != 0) eps += 1e-6 * (double)xmax * (double)xmax;
-      const double bound = (double)approx_last + eps;
       double kth = (double)ord2f((unsigned)(sorted[kk - 1] >> 32));
-      if (pp.metric != 0) kth = 0.5 * (kth + (double)pp.qstat[q * 4 + 3]);
+      if (pp.metric != 0) {
+        eps += 3.0e-8 * ((double)pp.qstat[q * 4 + 3] + fabs(kth));
+        kth = 0.5 * (kth + (double)pp.qstat[q * 4 + 3]);
+      }
+      const double bound = (double)approx_last + eps;
       if (m < pp.Mreq || !(bound < kth)) flag = 1;
       if (m >= pp.Mreq && kk < pp.k) flag = 1;
       if (kk >= pp.k && !ovf) theta = (float)(kth - eps - 1e-6 * (fabs(kth) + 1.0));
@@ -1876,9 +1879,14 @@ __global__ __launch_bounds__(256) void k_finalize(FinalParams p) {
       const float qn = p.qstat[q * 4 + 0], qh = p.qstat[q * 4 + 1], qe = p.qstat[q * 4 + 2];
       double eps = (double)xerr * qh + (double)xmax * qe + 2.0 * p.dimp * 5.9604645e-8 * (double)xmax * qn;
       if (p.metric != 0) eps += 1e-6 * (double)xmax * (double)xmax;  // f32 rounding of the stored -0.5||x||^2
-      const double bound = (double)p.approx[q * kMaxSel + m - 1] + eps;
       double kth = (double)ord2f((unsigned)(sel[kk - 1] >> 32));  // exact rank score of the k-th result
-      if (p.metric != 0) kth = 0.5 * (kth + (double)p.qstat[q * 4 + 3]);  // -dist -> q.x - 0.5||x||^2
+      if (p.metric != 0) {
+        // -dist -> q.x - 0.5||x||^2 from two float32 values, each within half a spacing (<= 2^-24 relative) of the number
+        // it stands for: the rank moves by up to 2^-25 (||q||^2 + dist), which no term above scales with when ||q|| >> ||x||
+        eps += 3.0e-8 * ((double)p.qstat[q * 4 + 3] + fabs(kth));
+        kth = 0.5 * (kth + (double)p.qstat[q * 4 + 3]);
+      }
+      const double bound = (double)p.approx[q * kMaxSel + m - 1] + eps;
       if (m < p.M || !(bound < kth)) flag = 1;
       if (m >= p.M && kk < p.k) flag = 1;
       // every row of the true top-k has exact rank >= kth, hence scan score >= kth - eps (rounded down a little)

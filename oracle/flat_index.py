@@ -54,18 +54,18 @@ def exact_scores(q: np.ndarray, x: np.ndarray, metric: str = "ip", block: int = 
     return out
 
 
-def flat_search(q: np.ndarray, x: np.ndarray, k: int, metric: str = "ip"):
+def flat_search(q: np.ndarray, x: np.ndarray, k: int, metric: str = "ip", scores: np.ndarray | None = None):
     """Exact top-k of preprocessed float32 rows: returns (D float32 [nq,k], I int64 [nq,k]).
 
     Order: best first; ties by ascending id; padding id -1 with the neutral score of faiss's heaps
-    (-FLT_MAX for IP, +FLT_MAX for L2).
+    (-FLT_MAX for IP, +FLT_MAX for L2).  `scores`: exact_scores(q, x, metric) where the caller already holds it.
     """
     nq, n = q.shape[0], x.shape[0]
     D = np.full((nq, k), -FLT_MAX if metric == "ip" else FLT_MAX, dtype=np.float32)
     I = np.full((nq, k), -1, dtype=np.int64)
     if n == 0 or nq == 0:
         return D, I
-    s = exact_scores(q, x, metric)
+    s = exact_scores(q, x, metric) if scores is None else scores
     s32 = s.astype(np.float32)  # the value reported (correctly rounded float32)
     kk = min(k, n)
     for i in range(nq):
@@ -196,3 +196,104 @@ def scan_image_error(x32: np.ndarray, bits: int = 12) -> float:
     x = np.asarray(x32, dtype=np.float32)
     d = scan_image(x, bits).astype(np.float64) - x.astype(np.float64)
     return float(np.sqrt((d * d).sum(axis=1)).max()) if len(x) else 0.0
+
+
+# ---- the certificate of the streaming scan, restated (csrc/index_kernels.hpp k_finalize / k_post; nothing of the reference) ----
+# The index nominates K' rows by their SCAN score — image row x f16 query, accumulated in float32 by the MFMA, plus for L2 the
+# float32 row bias -0.5 ||x||^2 — and certifies a query when  scan[K'-th] + eps < rank(k-th exact),  rank = q.x (IP) or
+# q.x - 0.5 ||x||^2 (L2).  That is sound when (1) |scan - rank| <= eps for every row, and (2, L2) the k-th rank the kernel
+# derives from the float32 values it holds, 0.5 * (float32 ||q||^2 - float32 dist), is off by no more than eps leaves over.
+EPS_TERMS = ("xerr", "qerr", "accum", "bias", "convert")
+
+
+def certificate_stats(x32: np.ndarray, bits: int = 16, image: np.ndarray | None = None):
+    """(xmax, xerr, usable) as k_add tracks them for stored float32 rows: the largest row norm and the largest
+    ||image row - row|| (for the 12- / 8-bit images the larger of that and the f16 image's, which the sample and the recovery
+    scans read), each with the kernel's 1.0001 slack, as float32; usable = no stored value beyond the f16 range.  `image`:
+    the decoded scan image where scan_image cannot restate it (bits = 8: tests/scan_image8.py)."""
+    x = np.asarray(x32, dtype=np.float32)
+    x64 = x.astype(np.float64)
+    xmax = np.float32(np.sqrt((x64 * x64).sum(axis=1)).max()) * np.float32(1.0001)
+    with np.errstate(over="ignore", invalid="ignore"):
+        err = [scan_image(x, 16).astype(np.float64) - x64]
+        if bits != 16:
+            err.append((scan_image(x, bits) if image is None else np.asarray(image)).astype(np.float64) - x64)
+        xerr = max(np.float32(np.sqrt((e * e).sum(axis=1)).max()) for e in err) * np.float32(1.0001)
+    return xmax, xerr, bool(np.abs(x).max() <= 65504.0)
+
+
+def certificate_eps(x32, q32, metric: str = "ip", bits: int = 16, image=None, kth=None, drop: str | None = None, stats=None):
+    """eps [nq] (float64) of the kernels' formula for preprocessed float32 rows / queries:
+        xerr ||q16|| + xmax ||q16 - q|| + 2 dimp 2^-24 xmax ||q||   (+ 1e-6 xmax^2 + 3e-8 (||q||^2 + |kth|) for L2)
+    `kth`: the k-th reported float32 squared distance per query (the last term is 0 without it).  `drop`: one of EPS_TERMS
+    left out — the mutants of tests/test_index_magnitudes_cpu.py.  `stats`: certificate_stats(x32, bits, image) where the
+    caller already holds it.  A query whose f16 image overflows gets inf or NaN, as on
+    the device (0 * inf when xerr == 0), which the kernels treat as "not certified"."""
+    q = np.asarray(q32, dtype=np.float32)
+    xmax, xerr, _ = certificate_stats(x32, bits, image) if stats is None else stats
+    dimp = -(-q.shape[1] // 128) * 128
+    with np.errstate(over="ignore", invalid="ignore"):
+        q64 = q.astype(np.float64)
+        h64 = q.astype(np.float16).astype(np.float64)
+        slack = np.float32(1.0001)
+        qn = np.sqrt((q64 * q64).sum(axis=1)).astype(np.float32) * slack
+        qh = np.sqrt((h64 * h64).sum(axis=1)).astype(np.float32) * slack
+        qe = np.sqrt(((h64 - q64) ** 2).sum(axis=1)).astype(np.float32) * slack
+        qn2 = (q64 * q64).sum(axis=1).astype(np.float32)
+        terms = {"xerr": float(xerr) * qh.astype(np.float64), "qerr": float(xmax) * qe.astype(np.float64),
+                 "accum": 2.0 * dimp * 5.9604645e-8 * float(xmax) * qn.astype(np.float64)}
+        if metric == "l2":
+            terms["bias"] = np.full(q.shape[0], 1e-6 * float(xmax) * float(xmax))
+            if kth is not None:
+                terms["convert"] = 3.0e-8 * (qn2.astype(np.float64) + np.abs(np.asarray(kth, dtype=np.float64)))
+        eps = np.zeros(q.shape[0])
+        for name, t in terms.items():
+            if name != drop:
+                eps = eps + t
+    return eps
+
+
+def scan_scores(x32, q32, metric: str = "ip", bits: int = 16, image=None, block: int = 4096) -> np.ndarray:
+    """The scan's score of every (query, row) pair, float32 [nq, n]: image row x f16 query accumulated as a float32 fma chain
+    in k order from 0 — the MFMA's numerics; a product of two f16 values is exact in float32, so `acc + a * b` in float32
+    IS the fused step — plus, for L2, the float32 row bias -0.5 * sum(v * v), itself a float32 chain in k order.  (A model
+    of the order: the device adds the bias terms in partial sums of eight; both are within the same worst-case bound.)
+    Queries whose f16 image is not finite get NaN."""
+    x = np.asarray(x32, dtype=np.float32)
+    q = np.asarray(q32, dtype=np.float32)
+    with np.errstate(over="ignore"):
+        qh = q.astype(np.float16).astype(np.float32)
+    bad = ~np.isfinite(qh).all(axis=1)
+    qh[bad] = 0.0
+    img = np.asarray(scan_image(x, bits) if image is None else image, dtype=np.float32)
+    out = np.empty((q.shape[0], x.shape[0]), dtype=np.float32)
+    prod = np.empty((q.shape[0], block), dtype=np.float32)
+    for s in range(0, x.shape[0], block):
+        it = np.ascontiguousarray(img[s:s + block].T)
+        m = it.shape[1]
+        acc = np.zeros((q.shape[0], m), dtype=np.float32)
+        for kk in range(it.shape[0]):
+            np.multiply(qh[:, kk:kk + 1], it[kk][None, :], out=prod[:, :m])
+            acc += prod[:, :m]
+        if metric == "l2":
+            xt = np.ascontiguousarray(x[s:s + block].T)
+            n2 = np.zeros(m, dtype=np.float32)
+            for kk in range(xt.shape[0]):
+                n2 += xt[kk] * xt[kk]
+            acc += (np.float32(-0.5) * n2)[None, :]
+        out[:, s:s + m] = acc
+    out[bad] = np.nan
+    return out
+
+
+def exact_ranks(x32, q32, metric: str = "ip", block: int = 65536) -> np.ndarray:
+    """float64 [nq, n]: the quantity the scan score approximates — q.x, or q.x - 0.5 ||x||^2 for L2"""
+    x = np.asarray(x32, dtype=np.float32)
+    q64 = np.asarray(q32, dtype=np.float32).astype(np.float64)
+    out = np.empty((q64.shape[0], x.shape[0]))
+    for s in range(0, x.shape[0], block):
+        xb = x[s:s + block].astype(np.float64)
+        out[:, s:s + block] = q64 @ xb.T
+        if metric == "l2":
+            out[:, s:s + block] -= 0.5 * (xb * xb).sum(axis=1)[None, :]
+    return out

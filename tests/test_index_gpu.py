@@ -4,6 +4,10 @@ Bar (BASELINE.json north_star): identical top-k id sets, scores within 1e-4 (flo
 ranks by the float64-accumulated score; rows closer than 1e-6 to the k-th score are near-ties that no
 float32 reference resolves reproducibly, so id sets are compared modulo those (none occur on the seeds
 used here unless a test says it builds them on purpose).
+
+Every case here is unit-scale Gaussian data, where an absolute 1e-4 is ~1000 float32 spacings.  The scale-free bar (ids
+position by position, scores to ONE float32 spacing) and the other magnitudes — subnormal to beyond the f16 range, integer
+and dyadic features, norms decades apart — are in tests/test_index_magnitudes_gpu.py (cases: tests/magnitude_cases.py).
 """
 import numpy as np
 import pytest
