@@ -3,3 +3,4 @@ from ._lib import AnoragError, METRIC_IP, METRIC_L2, device_count, load  # noqa:
 from .flat_index import FlatIndex  # noqa: F401
 from .ivf_index import IVFIndex  # noqa: F401
 from .graph_index import GraphIndex  # noqa: F401
+from .note_graph import NoteGraph  # noqa: F401

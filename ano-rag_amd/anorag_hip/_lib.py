@@ -33,6 +33,8 @@ OPT_SCHEDULE = 12
 OPT_STREAM_WAIT = 13
 OPT_SCAN_BITS = 14
 BATCH_LOG_FIELDS = 14
+ANR_ENOCONV = -5
+NOTEGRAPH_OPT_MAX_SLOTS = 1
 
 
 class AnoragError(RuntimeError):
@@ -235,6 +237,20 @@ SIGNATURES = {
     "anr_index_graph_knn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
     "anr_index_graph_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "anr_index_graph_stats": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "anr_notegraph_create": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.POINTER(C.c_void_p)]),
+    "anr_notegraph_destroy": (C.c_int, [C.c_void_p]),
+    "anr_notegraph_pagerank": (C.c_int, [C.c_void_p, C.c_double, C.c_int32, C.c_double, C.c_void_p, C.POINTER(C.c_int32)]),
+    "anr_notegraph_set_centrality": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "anr_notegraph_get_centrality": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "anr_notegraph_set_importance": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "anr_notegraph_retrieve": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "anr_notegraph_retrieve_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_int32,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "anr_notegraph_rows_to_array_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p]),
+    "anr_notegraph_set_option": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64]),
 }
 
 _lib = None

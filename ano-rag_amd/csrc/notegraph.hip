@@ -1,0 +1,826 @@
+// Note graph: the `graph` source of the score fusion (include/anorag.h, "Note graph").
+//
+//   graph   symmetric CSR on the device: rowptr int64 [n + 1], nbr int32 [2E], wt float64 [2E], neighbours ascending inside
+//           a row.  Built by one stable device sort of the 2E directed edges keyed (row << 32 | neighbour); a key that
+//           appears twice is a pair given twice.
+//   PageRank (graph/graph_index.py:46, networkx _pagerank_scipy).  a[p] = (1 / S_i) * w_ij for entry p = (row j, neighbour
+//           i) is formed once — a reciprocal times the weight, as scipy forms Q @ A — then every iteration is ONE pass over
+//           the CSR: one thread per row j adds x[i] * a[p] in ascending i, starting from 0.0.  The two reductions of an
+//           iteration (dangling mass, L1 change) are tree sums of one fixed shape (ng_tree below): no atomics, the same
+//           bits on every run and on every grid size.
+//   retrieve (graph/graph_retriever.py:61-92).  One SLOT per (query, valid seed): a [n] distance row (the bit pattern of a
+//           non-negative double orders like the double, so the relaxation is a 64-bit integer atomicMin), a round stamp
+//           that admits a node to the next frontier once per round, two frontiers and the list of touched nodes.  Rounds
+//           run for all slots of a sub-batch at once until every frontier is empty; min is order-independent, so the
+//           fixed point does not depend on the schedule.  The slots of a query are then merged in seed order through a
+//           per-query owner row (integer atomicMin of the seed position), and the query's nodes are ordered by four stable
+//           radix sorts (id, dist, seed position, score descending).  Slots and queries are reset from their touched /
+//           result lists, never by an n-wide fill.
+//
+// This file is compiled with -ffp-contract=off (csrc/Makefile): `a * b + c` is two roundings, as in the reference.
+#include <algorithm>
+#include <cmath>
+#include <limits>
+#include <mutex>
+#include <vector>
+
+#include "common.hpp"
+
+namespace anr {
+
+typedef unsigned long long u64;
+
+constexpr int kNgThreads = 256;
+constexpr int kNgChunk = 1024;               // elements per workgroup of a tree sum: 4 per thread
+constexpr u64 kNgInf = 0x7ff0000000000000ull;  // +inf: "not reached"
+constexpr int kNgLanes = 16;                 // lanes that share one frontier node's row
+constexpr int kNgMaxSlots = 32768;           // grid.y of the per-slot kernels
+
+// ---- CSR build -------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_ng_edge_keys(const int64_t *src, const int64_t *dst, int64_t E, u64 *keys,
+                                                      unsigned *vals) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= 2 * E) return;
+  const int64_t e = p < E ? p : p - E;
+  const u64 a = (u64)(p < E ? src[e] : dst[e]), b = (u64)(p < E ? dst[e] : src[e]);
+  keys[p] = (a << 32) | b;
+  vals[p] = (unsigned)p;
+}
+
+__global__ __launch_bounds__(256) void k_ng_csr_fill(const u64 *keys, const unsigned *vals, const double *w, int64_t E,
+                                                     int32_t *nbr, double *wt, int *dup) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= 2 * E) return;
+  nbr[p] = (int32_t)(keys[p] & 0xffffffffull);
+  const int64_t v = vals[p];
+  wt[p] = w[v < E ? v : v - E];
+  if (p > 0 && keys[p] == keys[p - 1]) *dup = 1;
+}
+
+// rowptr[i] = the first sorted entry whose row is >= i
+__global__ __launch_bounds__(256) void k_ng_rowptr(const u64 *keys, int64_t m, int64_t n, int64_t *rowptr) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i > n) return;
+  const u64 key = (u64)i << 32;
+  int64_t lo = 0, hi = m;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (keys[mid] < key) lo = mid + 1; else hi = mid;
+  }
+  rowptr[i] = lo;
+}
+
+// ---- fixed-shape sums ------------------------------------------------------------------------------------------------
+// ng_tree: the 256 values of a workgroup fold as v[t] += v[t + s] for s = 128, 64, ..., 1.  A chunk sum gives thread t the
+// elements t, t + 256, t + 512, t + 768 of its 1024-element chunk, added in that order, then folds; the chunk sums are
+// added the same way by one workgroup (thread t takes sums t, t + 256, ... in order, then the fold).  tests/notegraph_ref.py
+// restates exactly this.
+__device__ __forceinline__ double ng_tree(double v, double *sh) {
+  const int t = threadIdx.x;
+  sh[t] = v;
+  __syncthreads();
+  for (int s = kNgThreads / 2; s > 0; s >>= 1) {
+    if (t < s) sh[t] = sh[t] + sh[t + s];
+    __syncthreads();
+  }
+  const double r = sh[0];
+  __syncthreads();
+  return r;
+}
+
+__global__ __launch_bounds__(256) void k_ng_rowsum(const int64_t *rowptr, const double *wt, int64_t n, double *inv) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  double s = 0.0;
+  for (int64_t e = rowptr[i]; e < rowptr[i + 1]; ++e) s = s + wt[e];
+  inv[i] = s != 0.0 ? 1.0 / s : 0.0;  // 0.0 marks a dangling row (S == 0)
+}
+
+__global__ __launch_bounds__(256) void k_ng_scale(const int32_t *nbr, const double *wt, const double *inv, int64_t m,
+                                                  double *a) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p < m) a[p] = inv[nbr[p]] * wt[p];
+}
+
+__global__ __launch_bounds__(256) void k_ng_fill_f64(double *x, int64_t n, double v) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) x[i] = v;
+}
+
+// chunk sums of the dangling rows' x
+__global__ __launch_bounds__(256) void k_ng_dangling(const double *x, const double *inv, int64_t n, double *part) {
+  __shared__ double sh[kNgThreads];
+  double v = 0.0;
+  for (int k = 0; k < kNgChunk / kNgThreads; ++k) {
+    const int64_t i = (int64_t)blockIdx.x * kNgChunk + k * kNgThreads + threadIdx.x;
+    if (i < n && inv[i] == 0.0) v = v + x[i];
+  }
+  v = ng_tree(v, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = v;
+}
+
+// workgroup b adds the chunk sums part[b][0 .. nb) into out[b]
+__global__ __launch_bounds__(256) void k_ng_final(const double *part, int64_t nb, double *out) {
+  __shared__ double sh[kNgThreads];
+  const double *p = part + (int64_t)blockIdx.x * nb;
+  double v = 0.0;
+  for (int64_t i = threadIdx.x; i < nb; i += kNgThreads) v = v + p[i];
+  v = ng_tree(v, sh);
+  if (threadIdx.x == 0) out[blockIdx.x] = v;
+}
+
+struct NgStep {
+  const int64_t *rowptr;
+  const int32_t *nbr;
+  const double *a, *x, *inv, *scal;  // scal[1] = the dangling mass of x
+  double *xnew, *part;               // part[0][nb] L1 change, part[1][nb] dangling mass of xnew
+  double alpha, p, omp;              // p = 1 / n, omp = (1 - alpha) * p
+  int64_t n, nb;
+};
+
+__global__ __launch_bounds__(256) void k_ng_step(NgStep s) {
+  __shared__ double sh[kNgThreads];
+  const double dp = s.scal[1] * s.p;
+  double err = 0.0, dang = 0.0;
+  for (int k = 0; k < kNgChunk / kNgThreads; ++k) {
+    const int64_t j = (int64_t)blockIdx.x * kNgChunk + k * kNgThreads + threadIdx.x;
+    if (j >= s.n) continue;
+    double acc = 0.0;
+    for (int64_t e = s.rowptr[j]; e < s.rowptr[j + 1]; ++e) acc = acc + s.x[s.nbr[e]] * s.a[e];
+    const double xn = s.alpha * (acc + dp) + s.omp;
+    s.xnew[j] = xn;
+    err = err + fabs(xn - s.x[j]);
+    if (s.inv[j] == 0.0) dang = dang + xn;
+  }
+  err = ng_tree(err, sh);
+  dang = ng_tree(dang, sh);
+  if (threadIdx.x == 0) {
+    s.part[blockIdx.x] = err;
+    s.part[s.nb + blockIdx.x] = dang;
+  }
+}
+
+// ---- retrieve --------------------------------------------------------------------------------------------------------
+struct NgSlot {
+  int32_t seed, pos, q;  // node, position in the query's seed list, query slot of the batch
+};
+
+struct NgSearch {
+  const int64_t *rowptr;
+  const int32_t *nbr;
+  const double *wt;
+  int64_t n;
+  double cutoff;
+  u64 *dist;        // [slots][n]
+  int *stamp;       // [slots][n] last round that put the node into a frontier
+  int *touched;     // [slots][n] nodes reached (without the seed), in arrival order
+  int *fin, *fout;  // [slots][n]
+  int *cnt_in, *cnt_out, *tcnt;  // [slots]
+  const NgSlot *slot;
+  int nslots, round;
+  // merge
+  int *owner;       // [qslots][n] lowest seed position that reached the node
+  int *res_id, *res_pos;
+  double *res_dist;  // [qslots][n]
+  int *rcnt;         // [qslots]
+};
+
+__global__ __launch_bounds__(256) void k_ng_seed(NgSearch p) {
+  const int s = blockIdx.x * 256 + threadIdx.x;
+  if (s >= p.nslots) return;
+  const int64_t base = (int64_t)s * p.n;
+  p.dist[base + p.slot[s].seed] = 0ull;
+  p.fin[base] = p.slot[s].seed;
+  p.cnt_in[s] = 1;
+  p.cnt_out[s] = 0;
+  p.tcnt[s] = 0;
+}
+
+// one round: every frontier node u relaxes its row, kNgLanes lanes to a node
+__global__ __launch_bounds__(256) void k_ng_relax(NgSearch p) {
+  const int s = blockIdx.y;
+  const int64_t g = ((int64_t)blockIdx.x * 256 + threadIdx.x) / kNgLanes;
+  const int lane = threadIdx.x % kNgLanes;
+  if (g >= p.cnt_in[s]) return;
+  const int64_t base = (int64_t)s * p.n;
+  const int u = p.fin[base + g];
+  const double du = __longlong_as_double((long long)p.dist[base + u]);
+  for (int64_t e = p.rowptr[u] + lane; e < p.rowptr[u + 1]; e += kNgLanes) {
+    const double cand = du + p.wt[e];
+    if (!(cand <= p.cutoff)) continue;
+    const int v = p.nbr[e];
+    const u64 cb = (u64)__double_as_longlong(cand);
+    const u64 old = atomicMin(&p.dist[base + v], cb);
+    if (cb < old) {
+      if (old == kNgInf) p.touched[base + atomicAdd(&p.tcnt[s], 1)] = v;           // once per node: <= n - 1 entries
+      if (atomicMax(&p.stamp[base + v], p.round) < p.round)                          // once per node and round: <= n
+        p.fout[base + atomicAdd(&p.cnt_out[s], 1)] = v;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_ng_owner(NgSearch p) {
+  const int s = blockIdx.y;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= p.tcnt[s]) return;
+  const int v = p.touched[(int64_t)s * p.n + i];
+  atomicMin(&p.owner[(int64_t)p.slot[s].q * p.n + v], p.slot[s].pos);
+}
+
+__global__ __launch_bounds__(256) void k_ng_emit(NgSearch p) {
+  const int s = blockIdx.y;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= p.tcnt[s]) return;
+  const int64_t base = (int64_t)s * p.n, qb = (int64_t)p.slot[s].q * p.n;
+  const int v = p.touched[base + i];
+  if (p.owner[qb + v] != p.slot[s].pos) return;
+  const int j = atomicAdd(&p.rcnt[p.slot[s].q], 1);  // a node has one owner: <= n entries per query
+  p.res_id[qb + j] = v;
+  p.res_pos[qb + j] = p.slot[s].pos;
+  p.res_dist[qb + j] = __longlong_as_double((long long)p.dist[base + v]);
+}
+
+// the slot back to "nothing reached", from its touched list
+__global__ __launch_bounds__(256) void k_ng_reset(NgSearch p) {
+  const int s = blockIdx.y;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t base = (int64_t)s * p.n;
+  if (i == 0) p.dist[base + p.slot[s].seed] = kNgInf;
+  if (i >= p.tcnt[s]) return;
+  const int v = p.touched[base + i];
+  p.dist[base + v] = kNgInf;
+  p.stamp[base + v] = 0;
+}
+
+__global__ __launch_bounds__(256) void k_ng_fill_u64(u64 *x, int64_t n, u64 v) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) x[i] = v;
+}
+__global__ __launch_bounds__(256) void k_ng_fill_i32(int *x, int64_t n, int v) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) x[i] = v;
+}
+
+struct NgOrder {
+  const int *res_id, *res_pos;
+  const double *res_dist, *cent, *imp;
+  double *score;
+  int *owner;  // the query's owner row
+  int64_t f;
+};
+
+// graph_score of the query's f nodes (graph_retriever.py:87), the first sort key (id) and the owner row's reset
+__global__ __launch_bounds__(256) void k_ng_score(NgOrder o, u64 *keys, unsigned *vals) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= o.f) return;
+  const int id = o.res_id[j];
+  o.score[j] = (o.cent[id] / (o.res_dist[j] + 1e-5)) * o.imp[id];
+  keys[j] = (u64)id;
+  vals[j] = (unsigned)j;
+  o.owner[id] = 0x7fffffff;
+}
+
+// keys[i] of the next stable pass, read through the permutation so far: 0 dist, 1 seed position, 2 score (ascending
+// image of the double; the pass sorts it descending), 3 id
+__global__ __launch_bounds__(256) void k_ng_keys(NgOrder o, const unsigned *perm, int64_t m, int what, u64 *keys) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= m) return;
+  const unsigned j = perm[i];
+  u64 k;
+  if (what == 0) {
+    k = (u64)__double_as_longlong(o.res_dist[j]);
+  } else if (what == 1) {
+    k = (u64)o.res_pos[j];
+  } else if (what == 2) {
+    const u64 b = (u64)__double_as_longlong(o.score[j]);
+    k = (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+  } else {
+    k = (u64)o.res_id[j];
+  }
+  keys[i] = k;
+}
+
+__global__ __launch_bounds__(256) void k_ng_out_host(NgOrder o, const unsigned *perm, int64_t m, int64_t cap, int64_t *ids,
+                                                     double *dist, double *score, int32_t *pos) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= cap) return;
+  const bool live = i < m;
+  const unsigned j = live ? perm[i] : 0u;
+  ids[i] = live ? (int64_t)o.res_id[j] : -1;
+  dist[i] = live ? o.res_dist[j] : __longlong_as_double(0x7ff8000000000000ll);
+  score[i] = live ? o.score[j] : __longlong_as_double(0x7ff8000000000000ll);
+  pos[i] = live ? o.res_pos[j] : -1;
+}
+
+__global__ __launch_bounds__(256) void k_ng_out_dev(NgOrder o, const unsigned *perm, int64_t m, int64_t cap, uint32_t *ids,
+                                                    double *score, int32_t *count) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i == 0) *count = (int32_t)m;
+  if (i >= cap) return;
+  const bool live = i < m;
+  const unsigned j = live ? perm[i] : 0u;
+  ids[i] = live ? (uint32_t)o.res_id[j] : 0u;
+  score[i] = live ? o.score[j] : 0.0;
+}
+
+__global__ __launch_bounds__(256) void k_ng_scatter_rows(const uint32_t *ids, const double *scores, const int32_t *count,
+                                                         int64_t cap, int64_t n, double *out) {
+  const int64_t q = blockIdx.y;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= count[q] || i >= cap) return;
+  const uint32_t id = ids[q * cap + i];
+  if (id < n) out[q * n + id] = scores[q * cap + i];
+}
+
+}  // namespace anr
+
+using namespace anr;
+
+struct anr_notegraph {
+  int device = 0;
+  int64_t n = 0, E = 0, m = 0;  // m = 2E CSR entries
+  int64_t *rowptr = nullptr;
+  int32_t *nbr = nullptr;
+  double *wt = nullptr;
+  double *cent = nullptr, *imp = nullptr;
+  hipStream_t stream = nullptr;
+  std::mutex mu;
+  int64_t max_slots = 0;
+  // retrieve workspace, kept between calls; between calls every dist is +inf, every stamp 0, every owner INT_MAX
+  int ws_slots = 0, ws_q = 0;
+  bool ws_slots_limited = false, ws_q_limited = false;  // sized by free memory, not by the call that asked
+  int64_t ws_cap = 0;
+  u64 *dist = nullptr;
+  int *stamp = nullptr, *touched = nullptr, *fa = nullptr, *fb = nullptr;
+  int *cnt_a = nullptr, *cnt_b = nullptr, *tcnt = nullptr;
+  NgSlot *slot = nullptr;
+  int *owner = nullptr, *res_id = nullptr, *res_pos = nullptr, *rcnt = nullptr;
+  double *res_dist = nullptr;
+  u64 *key_a = nullptr, *key_b = nullptr;
+  unsigned *val_a = nullptr, *val_b = nullptr;
+  double *score = nullptr;
+  void *sort_temp = nullptr;
+  int64_t *o_ids = nullptr;  // [ws_q][ws_cap] staging of the host outputs
+  double *o_dist = nullptr, *o_score = nullptr;
+  int32_t *o_pos = nullptr;
+};
+
+namespace {
+
+template <typename T>
+int g_alloc(T **p, int64_t n) {
+  *p = nullptr;
+  ANR_HIP(hipMalloc(reinterpret_cast<void **>(p), (size_t)(n > 0 ? n : 1) * sizeof(T)));
+  return ANR_OK;
+}
+template <typename T>
+void g_free(T *&p) {
+  if (p) (void)hipFree(p);
+  p = nullptr;
+}
+
+inline unsigned blocks(int64_t n, int per = 256) { return (unsigned)std::max<int64_t>(1, ceil_div(n, per)); }
+
+void free_workspace(anr_notegraph *h) {
+  g_free(h->dist); g_free(h->stamp); g_free(h->touched); g_free(h->fa); g_free(h->fb);
+  g_free(h->cnt_a); g_free(h->cnt_b); g_free(h->tcnt); g_free(h->slot);
+  g_free(h->owner); g_free(h->res_id); g_free(h->res_pos); g_free(h->rcnt); g_free(h->res_dist);
+  g_free(h->key_a); g_free(h->key_b); g_free(h->val_a); g_free(h->val_b); g_free(h->score);
+  g_free(h->sort_temp);
+  g_free(h->o_ids); g_free(h->o_dist); g_free(h->o_score); g_free(h->o_pos);
+  h->ws_slots = h->ws_q = 0;
+  h->ws_cap = 0;
+  h->ws_slots_limited = h->ws_q_limited = false;
+}
+
+// bytes per (query, seed) slot, per query of a batch, and shared by all
+int64_t slot_bytes(int64_t n) { return 24 * n + 64; }
+int64_t query_bytes(int64_t n, int64_t cap) { return 20 * n + 28 * cap + 64; }
+int64_t shared_bytes(int64_t n) { return 32 * n + (int64_t)radix_sort_temp_bytes(n); }
+
+// Sizes the workspace for a call: `want_slots` searches and `want_q` queries would run it in one sub-batch.
+int ensure_workspace(anr_notegraph *h, int64_t want_slots, int64_t want_q, int64_t cap, bool host_out) {
+  const int64_t n = h->n;
+  want_slots = std::max<int64_t>(1, std::min<int64_t>(want_slots, kNgMaxSlots));
+  want_q = std::max<int64_t>(1, want_q);
+  if (h->max_slots > 0) {
+    want_slots = std::min(want_slots, h->max_slots);
+    want_q = std::min(want_q, h->max_slots);
+  }
+  const int64_t ocap = host_out ? cap : 0;
+  if (h->dist && (h->ws_slots >= want_slots || h->ws_slots_limited) && (h->ws_q >= want_q || h->ws_q_limited) &&
+      h->ws_cap >= ocap)
+    return ANR_OK;
+  // the held workspace is too small (or of another shape): sized anew from the memory that is free without it
+  free_workspace(h);
+  size_t free_b = 0, total_b = 0;
+  ANR_HIP(hipMemGetInfo(&free_b, &total_b));
+  const int64_t budget = (int64_t)(free_b / 2) - shared_bytes(n);
+  if (budget < query_bytes(n, ocap) + slot_bytes(n))
+    return fail(ANR_EHIP, "note graph: %lld bytes of free device memory do not hold one search slot of %lld nodes",
+                (long long)free_b, (long long)n);
+  // a quarter of the budget to the queries of a batch (owner row, result list, output staging), the rest to the slots
+  const int64_t nq_b = std::min(want_q, std::max<int64_t>(1, budget / 4 / query_bytes(n, ocap)));
+  const int64_t ns_b = std::min(want_slots, std::max<int64_t>(1, (budget - nq_b * query_bytes(n, ocap)) / slot_bytes(n)));
+  h->ws_q_limited = nq_b < want_q && !(h->max_slots > 0 && nq_b == h->max_slots);
+  h->ws_slots_limited = ns_b < want_slots;
+  ANR_TRY(g_alloc(&h->dist, ns_b * n));
+  ANR_TRY(g_alloc(&h->stamp, ns_b * n));
+  ANR_TRY(g_alloc(&h->touched, ns_b * n));
+  ANR_TRY(g_alloc(&h->fa, ns_b * n));
+  ANR_TRY(g_alloc(&h->fb, ns_b * n));
+  ANR_TRY(g_alloc(&h->cnt_a, ns_b));
+  ANR_TRY(g_alloc(&h->cnt_b, ns_b));
+  ANR_TRY(g_alloc(&h->tcnt, ns_b));
+  ANR_TRY(g_alloc(&h->slot, ns_b));
+  ANR_TRY(g_alloc(&h->owner, nq_b * n));
+  ANR_TRY(g_alloc(&h->res_id, nq_b * n));
+  ANR_TRY(g_alloc(&h->res_pos, nq_b * n));
+  ANR_TRY(g_alloc(&h->res_dist, nq_b * n));
+  ANR_TRY(g_alloc(&h->rcnt, nq_b));
+  ANR_TRY(g_alloc(&h->key_a, n));
+  ANR_TRY(g_alloc(&h->key_b, n));
+  ANR_TRY(g_alloc(&h->val_a, n));
+  ANR_TRY(g_alloc(&h->val_b, n));
+  ANR_TRY(g_alloc(&h->score, n));
+  ANR_HIP(hipMalloc(&h->sort_temp, radix_sort_temp_bytes(n)));
+  if (ocap > 0) {
+    ANR_TRY(g_alloc(&h->o_ids, nq_b * ocap));
+    ANR_TRY(g_alloc(&h->o_dist, nq_b * ocap));
+    ANR_TRY(g_alloc(&h->o_score, nq_b * ocap));
+    ANR_TRY(g_alloc(&h->o_pos, nq_b * ocap));
+  }
+  // the one n-wide fill of a slot's life: when it is allocated
+  hipLaunchKernelGGL(k_ng_fill_u64, dim3(blocks(ns_b * n)), dim3(256), 0, h->stream, h->dist, ns_b * n, kNgInf);
+  hipLaunchKernelGGL(k_ng_fill_i32, dim3(blocks(ns_b * n)), dim3(256), 0, h->stream, h->stamp, ns_b * n, 0);
+  hipLaunchKernelGGL(k_ng_fill_i32, dim3(blocks(nq_b * n)), dim3(256), 0, h->stream, h->owner, nq_b * n, 0x7fffffff);
+  ANR_HIP(hipGetLastError());
+  h->ws_slots = (int)ns_b;
+  h->ws_q = (int)nq_b;
+  h->ws_cap = ocap;
+  return ANR_OK;
+}
+
+// the searches of `ns` slots (already in h->slot) to their fixed point, merged into their queries' result lists
+int run_slots(anr_notegraph *h, const std::vector<NgSlot> &slots, int64_t s0, int ns, double cutoff) {
+  hipStream_t st = h->stream;
+  ANR_HIP(hipMemcpyAsync(h->slot, slots.data() + s0, (size_t)ns * sizeof(NgSlot), hipMemcpyHostToDevice, st));
+  NgSearch p{};
+  p.rowptr = h->rowptr; p.nbr = h->nbr; p.wt = h->wt; p.n = h->n; p.cutoff = cutoff;
+  p.dist = h->dist; p.stamp = h->stamp; p.touched = h->touched;
+  p.fin = h->fa; p.fout = h->fb; p.cnt_in = h->cnt_a; p.cnt_out = h->cnt_b; p.tcnt = h->tcnt;
+  p.slot = h->slot; p.nslots = ns; p.round = 0;
+  p.owner = h->owner; p.res_id = h->res_id; p.res_pos = h->res_pos; p.res_dist = h->res_dist; p.rcnt = h->rcnt;
+  hipLaunchKernelGGL(k_ng_seed, dim3(blocks(ns)), dim3(256), 0, st, p);
+  std::vector<int> cnt((size_t)ns);
+  int64_t maxc = 1;
+  while (maxc > 0) {
+    p.round += 1;
+    hipLaunchKernelGGL(k_ng_relax, dim3(blocks(maxc * kNgLanes), (unsigned)ns), dim3(256), 0, st, p);
+    ANR_HIP(hipMemcpyAsync(cnt.data(), p.cnt_out, (size_t)ns * sizeof(int), hipMemcpyDeviceToHost, st));
+    ANR_HIP(hipMemsetAsync(p.cnt_in, 0, (size_t)ns * sizeof(int), st));  // the next round's output counter
+    ANR_HIP(hipStreamSynchronize(st));
+    maxc = 0;
+    for (int c : cnt) maxc = std::max<int64_t>(maxc, c);
+    std::swap(p.fin, p.fout);
+    std::swap(p.cnt_in, p.cnt_out);
+  }
+  ANR_HIP(hipMemcpyAsync(cnt.data(), p.tcnt, (size_t)ns * sizeof(int), hipMemcpyDeviceToHost, st));
+  ANR_HIP(hipStreamSynchronize(st));
+  int64_t maxt = 0;
+  for (int c : cnt) maxt = std::max<int64_t>(maxt, c);
+  const dim3 grid(blocks(maxt), (unsigned)ns);
+  hipLaunchKernelGGL(k_ng_owner, grid, dim3(256), 0, st, p);
+  hipLaunchKernelGGL(k_ng_emit, grid, dim3(256), 0, st, p);
+  hipLaunchKernelGGL(k_ng_reset, grid, dim3(256), 0, st, p);
+  ANR_HIP(hipGetLastError());
+  return ANR_OK;
+}
+
+int check_seeds(const anr_notegraph *h, int64_t nq, const int64_t *seed_offs, const int64_t *seeds, double cutoff,
+                int64_t cap) {
+  if (!h || nq < 0 || !seed_offs) return fail(ANR_EINVAL, "bad argument");
+  if (seed_offs[0] != 0) return fail(ANR_EINVAL, "seed_offs[0] must be 0");
+  for (int64_t q = 0; q < nq; ++q) {
+    if (seed_offs[q + 1] < seed_offs[q]) return fail(ANR_EINVAL, "seed_offs must be non-decreasing");
+    if (seed_offs[q + 1] - seed_offs[q] > 0x7fffffffll) return fail(ANR_EINVAL, "too many seeds in one query");
+  }
+  if (seed_offs[nq] > 0 && !seeds) return fail(ANR_EINVAL, "null seeds");
+  if (!(cutoff >= 0.0)) return fail(ANR_EINVAL, "cutoff must be a non-negative number");
+  if (cap < 1) return fail(ANR_EINVAL, "cap must be >= 1");
+  return ANR_OK;
+}
+
+// Both retrieve entry points.  Host form: out_* host arrays; device form: ids_dev / scores_dev / count_dev.
+int retrieve_impl(anr_notegraph *h, int64_t nq, const int64_t *seed_offs, const int64_t *seeds, double cutoff,
+                  int64_t cap, bool host_out, int64_t *out_ids, double *out_dist, double *out_score, int32_t *out_pos,
+                  int32_t *out_count, uint32_t *ids_dev, double *scores_dev, int32_t *count_dev) {
+  if (nq == 0) return ANR_OK;
+  const int64_t n = h->n;
+  hipStream_t st = h->stream;
+  // the busiest batch this call could form: every query, every valid seed
+  int64_t valid = 0;
+  for (int64_t e = 0; e < seed_offs[nq]; ++e) valid += (seeds[e] >= 0 && seeds[e] < n);
+  ANR_TRY(ensure_workspace(h, valid, nq, cap, host_out));
+  std::vector<NgSlot> slots;
+  std::vector<int> found;
+  for (int64_t q0 = 0; q0 < nq; q0 += h->ws_q) {
+    const int nqb = (int)std::min<int64_t>(h->ws_q, nq - q0);
+    slots.clear();
+    for (int ql = 0; ql < nqb; ++ql)
+      for (int64_t e = seed_offs[q0 + ql]; e < seed_offs[q0 + ql + 1]; ++e)
+        if (seeds[e] >= 0 && seeds[e] < n)
+          slots.push_back(NgSlot{(int32_t)seeds[e], (int32_t)(e - seed_offs[q0 + ql]), ql});
+    ANR_HIP(hipMemsetAsync(h->rcnt, 0, (size_t)nqb * sizeof(int), st));
+    // slots in (query, seed position) order: an earlier sub-batch holds the earlier seeds of a query, so the owner row
+    // it leaves behind already belongs to them
+    for (int64_t s0 = 0; s0 < (int64_t)slots.size(); s0 += h->ws_slots)
+      ANR_TRY(run_slots(h, slots, s0, (int)std::min<int64_t>(h->ws_slots, (int64_t)slots.size() - s0), cutoff));
+    found.assign((size_t)nqb, 0);
+    ANR_HIP(hipMemcpyAsync(found.data(), h->rcnt, (size_t)nqb * sizeof(int), hipMemcpyDeviceToHost, st));
+    ANR_HIP(hipStreamSynchronize(st));
+    for (int ql = 0; ql < nqb; ++ql) {
+      const int64_t f = found[ql], m = std::min<int64_t>(f, cap), q = q0 + ql;
+      NgOrder o{};
+      o.res_id = h->res_id + (int64_t)ql * n; o.res_pos = h->res_pos + (int64_t)ql * n;
+      o.res_dist = h->res_dist + (int64_t)ql * n; o.cent = h->cent; o.imp = h->imp; o.score = h->score;
+      o.owner = h->owner + (int64_t)ql * n; o.f = f;
+      const unsigned *perm = h->val_a;
+      if (f > 0) {
+        // four stable passes, least significant key first: id, dist, seed position, score (descending)
+        hipLaunchKernelGGL(k_ng_score, dim3(blocks(f)), dim3(256), 0, st, o, h->key_a, h->val_a);
+        ANR_TRY(radix_sort_pairs_u64(h->sort_temp, h->key_a, h->key_b, h->val_a, h->val_b, f, false, st));
+        hipLaunchKernelGGL(k_ng_keys, dim3(blocks(f)), dim3(256), 0, st, o, h->val_b, f, 0, h->key_a);
+        ANR_TRY(radix_sort_pairs_u64(h->sort_temp, h->key_a, h->key_b, h->val_b, h->val_a, f, false, st));
+        hipLaunchKernelGGL(k_ng_keys, dim3(blocks(f)), dim3(256), 0, st, o, h->val_a, f, 1, h->key_a);
+        ANR_TRY(radix_sort_pairs_u64(h->sort_temp, h->key_a, h->key_b, h->val_a, h->val_b, f, false, st));
+        hipLaunchKernelGGL(k_ng_keys, dim3(blocks(f)), dim3(256), 0, st, o, h->val_b, f, 2, h->key_a);
+        ANR_TRY(radix_sort_pairs_u64(h->sort_temp, h->key_a, h->key_b, h->val_b, h->val_a, f, true, st));
+        if (!host_out) {  // the best m again, by id
+          hipLaunchKernelGGL(k_ng_keys, dim3(blocks(m)), dim3(256), 0, st, o, h->val_a, m, 3, h->key_a);
+          ANR_TRY(radix_sort_pairs_u64(h->sort_temp, h->key_a, h->key_b, h->val_a, h->val_b, m, false, st));
+          perm = h->val_b;
+        }
+      }
+      if (host_out) {
+        hipLaunchKernelGGL(k_ng_out_host, dim3(blocks(cap)), dim3(256), 0, st, o, perm, m, cap, h->o_ids + (int64_t)ql * cap,
+                           h->o_dist + (int64_t)ql * cap, h->o_score + (int64_t)ql * cap, h->o_pos + (int64_t)ql * cap);
+        out_count[q] = (int32_t)f;
+      } else {
+        hipLaunchKernelGGL(k_ng_out_dev, dim3(blocks(cap)), dim3(256), 0, st, o, perm, m, cap, ids_dev + q * cap,
+                           scores_dev + q * cap, count_dev + q);
+        if (out_count) out_count[q] = (int32_t)f;
+      }
+    }
+    ANR_HIP(hipGetLastError());
+    if (host_out) {
+      const size_t cnt = (size_t)nqb * (size_t)cap;
+      ANR_HIP(hipMemcpyAsync(out_ids + q0 * cap, h->o_ids, cnt * 8, hipMemcpyDeviceToHost, st));
+      if (out_dist) ANR_HIP(hipMemcpyAsync(out_dist + q0 * cap, h->o_dist, cnt * 8, hipMemcpyDeviceToHost, st));
+      if (out_score) ANR_HIP(hipMemcpyAsync(out_score + q0 * cap, h->o_score, cnt * 8, hipMemcpyDeviceToHost, st));
+      if (out_pos) ANR_HIP(hipMemcpyAsync(out_pos + q0 * cap, h->o_pos, cnt * 4, hipMemcpyDeviceToHost, st));
+    }
+    ANR_HIP(hipStreamSynchronize(st));
+  }
+  return ANR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int anr_notegraph_create(int32_t device, int64_t n_nodes, int64_t n_edges, const int64_t *src, const int64_t *dst,
+                         const double *w, anr_notegraph **out) {
+  if (!out) return fail(ANR_EINVAL, "out is null");
+  *out = nullptr;
+  if (n_nodes < 1 || n_nodes >= 0x7fffffffll) return fail(ANR_EINVAL, "n_nodes must be in [1, 2^31 - 1)");
+  if (n_edges < 0 || n_edges > (1ll << 30)) return fail(ANR_EINVAL, "n_edges must be in [0, 2^30]");
+  if (n_edges > 0 && (!src || !dst || !w)) return fail(ANR_EINVAL, "null edge arrays");
+  for (int64_t e = 0; e < n_edges; ++e) {
+    if (src[e] < 0 || src[e] >= n_nodes || dst[e] < 0 || dst[e] >= n_nodes)
+      return fail(ANR_EINVAL, "edge %lld: node id out of range", (long long)e);
+    if (src[e] == dst[e]) return fail(ANR_EINVAL, "edge %lld: self-loop on node %lld", (long long)e, (long long)src[e]);
+    if (!std::isfinite(w[e]) || w[e] < 0.0)
+      return fail(ANR_EINVAL, "edge %lld: weight must be finite and non-negative", (long long)e);
+  }
+  int ndev = anr_device_count();
+  if (ndev <= 0) return fail(ANR_EHIP, "no HIP device is visible");
+  if (device < 0 || device >= ndev) return fail(ANR_EINVAL, "device %d out of range", device);
+  DeviceGuard g(device);
+  anr_notegraph *h = new anr_notegraph();
+  h->device = device;
+  h->n = n_nodes;
+  h->E = n_edges;
+  h->m = 2 * n_edges;
+  const int64_t E = n_edges, m = h->m, n = n_nodes;
+  int64_t *d_src = nullptr, *d_dst = nullptr;
+  double *d_w = nullptr;
+  u64 *k0 = nullptr, *k1 = nullptr;
+  unsigned *v0 = nullptr, *v1 = nullptr;
+  void *temp = nullptr;
+  int *d_dup = nullptr;
+  int dup = 0;
+  auto body = [&]() -> int {
+    ANR_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    hipStream_t st = h->stream;
+    ANR_TRY(g_alloc(&h->rowptr, n + 1));
+    ANR_TRY(g_alloc(&h->nbr, m));
+    ANR_TRY(g_alloc(&h->wt, m));
+    ANR_TRY(g_alloc(&h->cent, n));
+    ANR_TRY(g_alloc(&h->imp, n));
+    ANR_HIP(hipMemsetAsync(h->cent, 0, (size_t)n * 8, st));
+    hipLaunchKernelGGL(k_ng_fill_f64, dim3(blocks(n)), dim3(256), 0, st, h->imp, n, 1.0);
+    ANR_TRY(g_alloc(&d_dup, 1));
+    ANR_HIP(hipMemsetAsync(d_dup, 0, sizeof(int), st));
+    if (E > 0) {
+      ANR_TRY(g_alloc(&d_src, E));
+      ANR_TRY(g_alloc(&d_dst, E));
+      ANR_TRY(g_alloc(&d_w, E));
+      ANR_TRY(g_alloc(&k0, m));
+      ANR_TRY(g_alloc(&k1, m));
+      ANR_TRY(g_alloc(&v0, m));
+      ANR_TRY(g_alloc(&v1, m));
+      ANR_HIP(hipMalloc(&temp, radix_sort_temp_bytes(m)));
+      ANR_HIP(hipMemcpyAsync(d_src, src, (size_t)E * 8, hipMemcpyHostToDevice, st));
+      ANR_HIP(hipMemcpyAsync(d_dst, dst, (size_t)E * 8, hipMemcpyHostToDevice, st));
+      ANR_HIP(hipMemcpyAsync(d_w, w, (size_t)E * 8, hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL(k_ng_edge_keys, dim3(blocks(m)), dim3(256), 0, st, d_src, d_dst, E, k0, v0);
+      ANR_TRY(radix_sort_pairs_u64(temp, k0, k1, v0, v1, m, false, st));
+      hipLaunchKernelGGL(k_ng_csr_fill, dim3(blocks(m)), dim3(256), 0, st, k1, v1, d_w, E, h->nbr, h->wt, d_dup);
+    }
+    hipLaunchKernelGGL(k_ng_rowptr, dim3(blocks(n + 1)), dim3(256), 0, st, k1, m, n, h->rowptr);
+    ANR_HIP(hipGetLastError());
+    ANR_HIP(hipMemcpyAsync(&dup, d_dup, sizeof(int), hipMemcpyDeviceToHost, st));
+    ANR_HIP(hipStreamSynchronize(st));
+    return ANR_OK;
+  };
+  int rc = body();
+  g_free(d_src); g_free(d_dst); g_free(d_w); g_free(k0); g_free(k1); g_free(v0); g_free(v1); g_free(d_dup);
+  if (temp) (void)hipFree(temp);
+  if (rc == ANR_OK && dup) rc = fail(ANR_EINVAL, "an undirected pair is given more than once");
+  if (rc != ANR_OK) {
+    anr_notegraph_destroy(h);
+    return rc;
+  }
+  *out = h;
+  return ANR_OK;
+}
+
+int anr_notegraph_destroy(anr_notegraph *h) {
+  if (!h) return ANR_OK;
+  DeviceGuard g(h->device);
+  if (h->stream) (void)hipStreamSynchronize(h->stream);
+  free_workspace(h);
+  g_free(h->rowptr); g_free(h->nbr); g_free(h->wt); g_free(h->cent); g_free(h->imp);
+  if (h->stream) (void)hipStreamDestroy(h->stream);
+  delete h;
+  return ANR_OK;
+}
+
+int anr_notegraph_pagerank(anr_notegraph *h, double alpha, int32_t max_iter, double tol, double *out_host, int32_t *iters) {
+  if (!h) return fail(ANR_EINVAL, "null handle");
+  if (!(alpha >= 0.0 && alpha <= 1.0) || max_iter < 0 || !(tol >= 0.0)) return fail(ANR_EINVAL, "bad PageRank parameter");
+  std::lock_guard<std::mutex> lk(h->mu);
+  DeviceGuard g(h->device);
+  hipStream_t st = h->stream;
+  const int64_t n = h->n, m = h->m, nb = ceil_div(n, kNgChunk);
+  double *inv = nullptr, *a = nullptr, *x = nullptr, *xn = nullptr, *part = nullptr, *scal = nullptr;
+  int done = 0;
+  bool converged = false;
+  auto body = [&]() -> int {
+    ANR_TRY(g_alloc(&inv, n));
+    ANR_TRY(g_alloc(&a, m));
+    ANR_TRY(g_alloc(&x, n));
+    ANR_TRY(g_alloc(&xn, n));
+    ANR_TRY(g_alloc(&part, 2 * nb));
+    ANR_TRY(g_alloc(&scal, 2));
+    const double p = 1.0 / (double)n;
+    hipLaunchKernelGGL(k_ng_rowsum, dim3(blocks(n)), dim3(256), 0, st, h->rowptr, h->wt, n, inv);
+    if (m > 0) hipLaunchKernelGGL(k_ng_scale, dim3(blocks(m)), dim3(256), 0, st, h->nbr, h->wt, inv, m, a);
+    hipLaunchKernelGGL(k_ng_fill_f64, dim3(blocks(n)), dim3(256), 0, st, x, n, p);
+    hipLaunchKernelGGL(k_ng_dangling, dim3((unsigned)nb), dim3(256), 0, st, x, inv, n, part + nb);
+    hipLaunchKernelGGL(k_ng_final, dim3(1), dim3(256), 0, st, part + nb, nb, scal + 1);
+    NgStep s{};
+    s.rowptr = h->rowptr; s.nbr = h->nbr; s.a = a; s.inv = inv; s.scal = scal; s.part = part;
+    s.alpha = alpha; s.p = p; s.omp = (1.0 - alpha) * p; s.n = n; s.nb = nb;
+    for (int it = 0; it < max_iter && !converged; ++it) {
+      s.x = x;
+      s.xnew = xn;
+      hipLaunchKernelGGL(k_ng_step, dim3((unsigned)nb), dim3(256), 0, st, s);
+      hipLaunchKernelGGL(k_ng_final, dim3(2), dim3(256), 0, st, part, nb, scal);
+      double err = 0.0;
+      ANR_HIP(hipMemcpyAsync(&err, scal, 8, hipMemcpyDeviceToHost, st));
+      ANR_HIP(hipStreamSynchronize(st));
+      std::swap(x, xn);
+      done = it + 1;
+      converged = err < (double)n * tol;
+    }
+    ANR_HIP(hipGetLastError());
+    if (converged) {
+      ANR_HIP(hipMemcpyAsync(h->cent, x, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+      if (out_host) ANR_HIP(hipMemcpyAsync(out_host, x, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+      ANR_HIP(hipStreamSynchronize(st));
+    }
+    return ANR_OK;
+  };
+  int rc = body();
+  g_free(inv); g_free(a); g_free(x); g_free(xn); g_free(part); g_free(scal);
+  if (iters) *iters = done;
+  if (rc != ANR_OK) return rc;
+  if (!converged) return fail(ANR_ENOCONV, "PageRank did not converge within %d iterations", (int)max_iter);
+  return ANR_OK;
+}
+
+int anr_notegraph_set_centrality(anr_notegraph *h, const double *c_host) {
+  if (!h || !c_host) return fail(ANR_EINVAL, "bad argument");
+  std::lock_guard<std::mutex> lk(h->mu);
+  DeviceGuard g(h->device);
+  ANR_HIP(hipMemcpyAsync(h->cent, c_host, (size_t)h->n * 8, hipMemcpyHostToDevice, h->stream));
+  ANR_HIP(hipStreamSynchronize(h->stream));
+  return ANR_OK;
+}
+
+int anr_notegraph_get_centrality(anr_notegraph *h, double *c_host) {
+  if (!h || !c_host) return fail(ANR_EINVAL, "bad argument");
+  std::lock_guard<std::mutex> lk(h->mu);
+  DeviceGuard g(h->device);
+  ANR_HIP(hipMemcpyAsync(c_host, h->cent, (size_t)h->n * 8, hipMemcpyDeviceToHost, h->stream));
+  ANR_HIP(hipStreamSynchronize(h->stream));
+  return ANR_OK;
+}
+
+int anr_notegraph_set_importance(anr_notegraph *h, const double *imp_host) {
+  if (!h || !imp_host) return fail(ANR_EINVAL, "bad argument");
+  std::lock_guard<std::mutex> lk(h->mu);
+  DeviceGuard g(h->device);
+  ANR_HIP(hipMemcpyAsync(h->imp, imp_host, (size_t)h->n * 8, hipMemcpyHostToDevice, h->stream));
+  ANR_HIP(hipStreamSynchronize(h->stream));
+  return ANR_OK;
+}
+
+int anr_notegraph_retrieve(anr_notegraph *h, int64_t nq, const int64_t *seed_offs, const int64_t *seeds, double cutoff,
+                           int32_t cap, int64_t *out_ids, double *out_dist, double *out_score, int32_t *out_seed_pos,
+                           int32_t *out_count) {
+  ANR_TRY(check_seeds(h, nq, seed_offs, seeds, cutoff, cap));
+  if (nq > 0 && (!out_ids || !out_count)) return fail(ANR_EINVAL, "null output");
+  std::lock_guard<std::mutex> lk(h->mu);
+  DeviceGuard g(h->device);
+  int rc = retrieve_impl(h, nq, seed_offs, seeds, cutoff, cap, true, out_ids, out_dist, out_score, out_seed_pos, out_count,
+                         nullptr, nullptr, nullptr);
+  if (rc != ANR_OK) {  // a workspace left half-way does not hold its invariants: the next call builds a new one
+    (void)hipStreamSynchronize(h->stream);
+    free_workspace(h);
+  }
+  return rc;
+}
+
+int anr_notegraph_retrieve_dev(anr_notegraph *h, int64_t nq, const int64_t *seed_offs, const int64_t *seeds,
+                               double cutoff, int32_t cap, uint32_t *ids_dev, double *scores_dev, int32_t *count_dev,
+                               int32_t *out_found_host) {
+  ANR_TRY(check_seeds(h, nq, seed_offs, seeds, cutoff, cap));
+  if (cap > 65536) return fail(ANR_EINVAL, "cap must be <= 65536 (anr_fuse_source.sparse_cap)");
+  if (nq > 0 && (!ids_dev || !scores_dev || !count_dev)) return fail(ANR_EINVAL, "null output");
+  std::lock_guard<std::mutex> lk(h->mu);
+  DeviceGuard g(h->device);
+  int rc = retrieve_impl(h, nq, seed_offs, seeds, cutoff, cap, false, nullptr, nullptr, nullptr, nullptr, out_found_host,
+                         ids_dev, scores_dev, count_dev);
+  if (rc != ANR_OK) {
+    (void)hipStreamSynchronize(h->stream);
+    free_workspace(h);
+  }
+  return rc;
+}
+
+int anr_notegraph_rows_to_array_dev(anr_notegraph *h, int64_t nq, int32_t cap, const uint32_t *ids_dev,
+                                    const double *scores_dev, const int32_t *count_dev, double *out_dev) {
+  if (!h || nq < 0 || cap < 1) return fail(ANR_EINVAL, "bad argument");
+  if (nq == 0) return ANR_OK;
+  if (!ids_dev || !scores_dev || !count_dev || !out_dev) return fail(ANR_EINVAL, "null argument");
+  if (nq > 65535) return fail(ANR_EINVAL, "at most 65535 queries per call");
+  std::lock_guard<std::mutex> lk(h->mu);
+  DeviceGuard g(h->device);
+  hipStream_t st = h->stream;
+  hipLaunchKernelGGL(k_ng_fill_f64, dim3(blocks(nq * h->n)), dim3(256), 0, st, out_dev, nq * h->n,
+                     std::numeric_limits<double>::quiet_NaN());
+  hipLaunchKernelGGL(k_ng_scatter_rows, dim3(blocks(cap), (unsigned)nq), dim3(256), 0, st, ids_dev, scores_dev, count_dev,
+                     (int64_t)cap, h->n, out_dev);
+  ANR_HIP(hipGetLastError());
+  ANR_HIP(hipStreamSynchronize(st));
+  return ANR_OK;
+}
+
+int anr_notegraph_set_option(anr_notegraph *h, int32_t option, int64_t value) {
+  if (!h) return fail(ANR_EINVAL, "null handle");
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (option == ANR_NOTEGRAPH_OPT_MAX_SLOTS) {
+    if (value < 0) return fail(ANR_EINVAL, "max slots must be >= 0");
+    DeviceGuard g(h->device);
+    (void)hipStreamSynchronize(h->stream);
+    free_workspace(h);  // the next retrieve sizes it under the new bound
+    h->max_slots = value;
+    return ANR_OK;
+  }
+  return fail(ANR_EINVAL, "unknown note graph option %d", (int)option);
+}
+
+}  // extern "C"

@@ -535,6 +535,76 @@ typedef struct anr_graph_stats {
 } anr_graph_stats;
 int anr_index_graph_stats(anr_index *h, anr_graph_stats *out);
 
+/* ------------------------------------------------------------------------------------------------
+ * Note graph (opt-in): the `graph` source of HybridSearcher.fuse — GraphIndex.build_index's weighted PageRank
+ * (graph/graph_index.py:43-49) and GraphRetriever.retrieve's bounded shortest-path expansion from seed notes
+ * (graph/graph_retriever.py:61-92), float64 throughout, on an undirected weighted graph kept as a symmetric CSR on the
+ * device (int64 row offsets, int32 neighbour, float64 weight, neighbours ascending inside a row).  Unrelated to the
+ * anr_index_graph_* vector index above.  Layouts, summation orders and the workspace rule: DESIGN.md §5e and the top of
+ * csrc/notegraph.hip.  Calls on one handle are serialised.
+ * Out of scope: the reference's fallbacks for graphs networkx cannot weigh (unweighted PageRank, graph_index.py:47-49;
+ * hop-count BFS, graph_retriever.py:75-77) — such graphs are rejected at create instead; directed graphs; personalised
+ * PageRank; the reasoning-path search.
+ * ---------------------------------------------------------------------------------------------- */
+#define ANR_ENOCONV (-5)  /* anr_notegraph_pagerank: no convergence within max_iter (networkx raises
+                             PowerIterationFailedConvergence there) */
+typedef struct anr_notegraph anr_notegraph;
+/* the nx.Graph the reference builds (graph/graph_builder.py:21-35) as its n_edges undirected edges: distinct unordered
+ * pairs (src[e], dst[e]) with ids in [0, n_nodes) (the caller maps note ids to node indices, graph_index.py:28-35) and
+ * weight w[e].  ANR_EINVAL for a self-loop, a pair given twice (in either direction), a negative or non-finite weight, an
+ * id out of range; n_nodes < 2^31 - 1, n_edges <= 2^30. */
+int anr_notegraph_create(int32_t device, int64_t n_nodes, int64_t n_edges, const int64_t *src, const int64_t *dst,
+                         const double *w, anr_notegraph **out);
+int anr_notegraph_destroy(anr_notegraph *h);
+/* nx.pagerank(graph, weight="weight") of graph_index.py:46 (networkx 3.x _pagerank_scipy, uniform personalisation and
+ * dangling weights, start 1/n): x <- alpha * (x A + sum_dangling(x) * p) + (1 - alpha) * p with A[i][j] = (1 / S_i) * w_ij,
+ * S_i the sum of row i in ascending j, dangling = the rows with S_i == 0, until the L1 change is < n * tol.  Pull form:
+ * x_new[j] adds x[i] * A[i][j] over row j in ascending i, one thread per row; the dangling sum and the L1 change are
+ * fixed-shape tree sums (no float atomics, no multiply-add contraction), so the result is the same bits on every run.
+ * The result becomes the handle's centrality and, when out_host is not NULL, is copied to out_host [n].  *iters (may be
+ * NULL): iterations made.  ANR_ENOCONV after max_iter iterations without convergence (the handle's centrality is then
+ * left as it was). */
+int anr_notegraph_pagerank(anr_notegraph *h, double alpha, int32_t max_iter, double tol, double *out_host, int32_t *iters);
+/* the centrality graph_retriever.py:84 looks up (GraphIndex.get_centrality), [n] float64: supplied from elsewhere / read
+ * back.  Zero until a PageRank or a set. */
+int anr_notegraph_set_centrality(anr_notegraph *h, const double *c_host);
+int anr_notegraph_get_centrality(anr_notegraph *h, double *c_host);
+/* the nodes' importance_score (graph_retriever.py:86), [n] float64; 1.0 per node until set */
+int anr_notegraph_set_importance(anr_notegraph *h, const double *imp_host);
+/* GraphRetriever.retrieve (graph_retriever.py:66-90) for nq seed lists at once: query q has the seeds
+ * seeds[seed_offs[q] .. seed_offs[q+1]) in list order; a seed < 0 or >= n is skipped (:69-70).  Per seed one bounded
+ * single-source shortest-path search (:72-74, cutoff = k_hop is a DISTANCE): label-correcting relaxations
+ * d[v] = min(d[v], d[u] + w) from nodes with d[u] <= cutoff, candidates > cutoff dropped — the fixed point is Dijkstra's
+ * distance bit for bit.  A node is reported once per query, with the distance from the first seed in list order that
+ * reaches it; a search never reports its own seed and does not mark it visited (:79-81).
+ * graph_score = (centrality / (dist + 1e-5)) * importance (:87), three float64 operations in that order.
+ * Per query, best first by (score descending, seed position ascending, dist ascending, id ascending): out_ids /
+ * out_dist / out_score / out_seed_pos [nq][cap], padded with -1 / NaN / NaN / -1; out_count[q] = the nodes found, which
+ * may exceed cap (the best cap are kept).  out_dist, out_score, out_seed_pos may be NULL. */
+int anr_notegraph_retrieve(anr_notegraph *h, int64_t nq, const int64_t *seed_offs, const int64_t *seeds, double cutoff,
+                           int32_t cap, int64_t *out_ids, double *out_dist, double *out_score, int32_t *out_seed_pos,
+                           int32_t *out_count);
+/* the same result left on the handle's device as rows ASCENDING BY ID: ids_dev uint32 [nq][cap], scores_dev float64
+ * [nq][cap] (graph_score), count_dev int32 [nq] = min(found, cap) — the layout of anr_fuse_source.sparse_* (cap <= 65536).
+ * out_found_host (may be NULL): the nodes found per query, before the cap. */
+int anr_notegraph_retrieve_dev(anr_notegraph *h, int64_t nq, const int64_t *seed_offs, const int64_t *seeds,
+                               double cutoff, int32_t cap, uint32_t *ids_dev, double *scores_dev, int32_t *count_dev,
+                               int32_t *out_found_host);
+/* Hand-off to anr_fuse_dense as its `graph` source.  The sparse form cannot carry these rows as they are: there every id
+ * that is not listed holds 0.0 and is therefore PRESENT, while a note the expansion did not reach must be ABSENT from
+ * `graph` (hybrid_search.py tags a result's sources by membership, and an id that only `graph` lists with 0.0 would become
+ * a candidate).  Of the two ways round it — (a) a dense [nq][n] float64 array with NaN for the absent ids, (b) a short host
+ * list — this is (a): a list is limited to 1024 entries per query and one seed already reaches thousands of notes, and
+ * the array stays on the device.  Fills out_dev [nq][n] (caller-allocated on the handle's device) with NaN and scatters
+ * the rows of anr_notegraph_retrieve_dev into it: hand it over as anr_fuse_source.array_dev with array_len = n.  Cost:
+ * 8 n bytes written per query, and the fusion streams them again. */
+int anr_notegraph_rows_to_array_dev(anr_notegraph *h, int64_t nq, int32_t cap, const uint32_t *ids_dev,
+                                    const double *scores_dev, const int32_t *count_dev, double *out_dev);
+/* options: 1 = ANR_NOTEGRAPH_OPT_MAX_SLOTS — an upper bound on the (query, seed) searches in flight at a time (0 = sized
+ * from free device memory; tests force 1 to walk the sub-batching).  Results never depend on it. */
+#define ANR_NOTEGRAPH_OPT_MAX_SLOTS 1
+int anr_notegraph_set_option(anr_notegraph *h, int32_t option, int64_t value);
+
 #ifdef __cplusplus
 }
 #endif
