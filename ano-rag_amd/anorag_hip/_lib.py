@@ -131,6 +131,7 @@ SIGNATURES = {
         C.c_int,
         [C.c_void_p, C.c_float, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)],
     ),
+    "anr_index_dbscan": (C.c_int, [C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_void_p]),
     "anr_index_set_option": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64]),
     "anr_index_last_stats": (C.c_int, [C.c_void_p, C.POINTER(SearchStats)]),
     "anr_index_reconstruct_scan_image": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p]),

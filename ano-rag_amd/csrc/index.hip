@@ -18,6 +18,7 @@
 #include <mutex>
 #include <vector>
 
+#include "cluster.hpp"
 #include "common.hpp"
 #include "graph.hpp"
 #include "index_kernels.hpp"
@@ -2139,5 +2140,19 @@ IndexCore index_core(anr_index *h) {
 }
 
 anr_graph *&index_graph(anr_index *h) { return h->graph; }
+
+int index_join_view(anr_index *h, JoinView *out) {
+  ANR_TRY(drain(h));
+  ANR_TRY(refresh_xstat(h));
+  unsigned xs[2] = {0, 0};
+  ANR_HIP(hipMemcpy(xs, h->xstat, sizeof xs, hipMemcpyDeviceToHost));
+  float xmax, xerr;
+  memcpy(&xmax, &xs[0], 4);
+  memcpy(&xerr, &xs[1], 4);
+  *out = JoinView{h->x32, reinterpret_cast<const uint4 *>(h->x16), h->metric == ANR_METRIC_L2 ? h->rowbias : nullptr,
+                  h->ntotal, h->dim, h->dimp, h->kb, h->metric, h->normalize, h->n_cu, xmax, xerr, h->f16_unusable,
+                  h->stream};
+  return ANR_OK;
+}
 
 }  // namespace anr

@@ -131,6 +131,22 @@ int anr_similarity_matrix(int32_t device, const float *a_host, int64_t m, const 
 int anr_index_self_join(anr_index *h, float threshold, int64_t cap, int64_t *I_host, int64_t *J_host,
                         float *S_host, int64_t *n_pairs);
 
+/* DBSCAN topic clustering of the stored rows: what sklearn's DBSCAN(eps, min_samples, metric).fit_predict returns in the
+ * `dbscan` branch of TopicClustering._cpu_clustering (doc/clustering.py:88-99; reached from cluster_notes, :22-29, which
+ * DocumentProcessor.process_documents calls on every build, doc/document_processor.py:181; the reference's GPU path,
+ * utils/gpu_utils.py:123-152, is cuML and does not exist on ROCm).  Distance: Euclidean on an L2 index; on an
+ * inner-product index with normalize = 1 the cosine distance 1 - x_i . x_j of the stored rows; an inner-product index
+ * without normalisation is ANR_EINVAL.  A row is a core row if at least min_samples rows (itself included) lie within
+ * eps of it; clusters are the connected components of the core rows under "within eps", numbered from 0 in the order of
+ * their smallest core row; a row that is not core takes the smallest label among its core neighbours, or -1 (noise).
+ * The decision D <= eps is the float64 one on the stored float32 rows: pairs the f16 image cannot decide are re-scored.
+ * The eps pairs are consumed on the device: memory beyond the index is O(ntotal) plus the list of re-scored pairs.
+ * labels_host: int32 [ntotal].  stats (8 words, may be NULL): [0] clusters, [1] core rows, [2] noise rows, [3] pairs
+ * re-scored, [4] tile walks run, [5] pointer-jumping rounds, [6] times the re-score list was regrown, [7] re-scored
+ * pairs found within eps.  ANR_EINVAL: eps NaN or negative, min_samples < 1.  ANR_ESTATE: a stored value is outside the
+ * f16 range.  ntotal == 0: ANR_OK, nothing written. */
+int anr_index_dbscan(anr_index *h, double eps, int32_t min_samples, int32_t *labels_host, int64_t *stats);
+
 /* tuning / introspection */
 #define ANR_OPT_FORCE_EXACT 1     /* 1: skip the f16 scan, run the dense exact path for every query  */
 #define ANR_OPT_OVERFETCH 2       /* candidates kept per query before the exact re-score (0 = auto)  */
