@@ -82,6 +82,11 @@ class FuseDenseStats(C.Structure):
                 ("scan_ms", C.c_float)]
 
 
+class DiversityParams(C.Structure):
+    _fields_ = [("max_candidates", C.c_int32), ("dedup", C.c_int32), ("quota", C.c_int32), ("reserved", C.c_int32),
+                ("similarity_threshold", C.c_double), ("balance_factor", C.c_double), ("quotas", C.c_int32 * 32)]
+
+
 class EncoderConfig(C.Structure):
     _fields_ = [
         ("n_layers", C.c_int32), ("hidden", C.c_int32), ("n_heads", C.c_int32), ("intermediate", C.c_int32),
@@ -132,6 +137,9 @@ SIGNATURES = {
         [C.c_void_p, C.c_float, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)],
     ),
     "anr_index_dbscan": (C.c_int, [C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_void_p]),
+    "anr_index_diversify": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "anr_diversify_timing": (C.c_int, [C.c_int32, C.c_void_p]),
     "anr_index_set_option": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64]),
     "anr_index_last_stats": (C.c_int, [C.c_void_p, C.POINTER(SearchStats)]),
     "anr_index_reconstruct_scan_image": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p]),

@@ -100,6 +100,11 @@ class FlatIndex:
                                                   out.ctypes.data), "anr_index_score_rows")
         return out
 
+    def diversify(self, rows, scores, type_masks=None, **kwargs):
+        """semantic dedup and greedy diverse selection over stored rows: ``anorag_hip.diversity.diversify`` on this index"""
+        from .diversity import diversify
+        return diversify(self, rows, scores, type_masks, **kwargs)
+
     def self_join(self, threshold: float, cap_hint: int = 0, sort: bool = True):
         """all pairs i < j of stored rows with inner product >= threshold: (i, j, score) arrays, sorted by (i, j)
         unless sort=False (device order)"""

@@ -20,6 +20,7 @@
 
 #include "cluster.hpp"
 #include "common.hpp"
+#include "diversity.hpp"
 #include "graph.hpp"
 #include "index_kernels.hpp"
 #include "tiny_kernels.hpp"
@@ -157,6 +158,7 @@ struct anr_index {
 
   anr_search_stats stats{};
   anr_graph *graph = nullptr;  // graph index on these rows (graph.hip); adds and resets mark it stale
+  anr_diversity *diversity = nullptr;  // scratch of anr_index_diversify (diversity.hip)
 };
 
 namespace {
@@ -1590,6 +1592,7 @@ int anr_index_destroy(anr_index *h) {
   dev_free(h->tiny_ticket);
   dev_free(h->tiny_stamps);
   graph_free(h->graph);
+  diversity_free(h->diversity);
   for (auto &e : h->ev_call)
     if (e) (void)hipEventDestroy(e);
   for (hipStream_t s : {h->bstream[0], h->bstream[1], h->bstream[2], h->stream})
@@ -2140,6 +2143,8 @@ IndexCore index_core(anr_index *h) {
 }
 
 anr_graph *&index_graph(anr_index *h) { return h->graph; }
+
+anr_diversity *&index_diversity(anr_index *h) { return h->diversity; }
 
 int index_join_view(anr_index *h, JoinView *out) {
   ANR_TRY(drain(h));

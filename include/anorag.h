@@ -147,6 +147,51 @@ int anr_index_self_join(anr_index *h, float threshold, int64_t cap, int64_t *I_h
  * f16 range.  ntotal == 0: ANR_OK, nothing written. */
 int anr_index_dbscan(anr_index *h, double eps, int32_t min_samples, int32_t *labels_host, int64_t *stats);
 
+/* Diversity scheduling of fused candidates: the arithmetic of DiversityScheduler.schedule_candidates
+ * (retrieval/diversity_scheduler.py:523, called from query/query_processor.py:3367) for a batch of nq queries, each with
+ * a ragged candidate list offs[q] .. offs[q + 1] (offs has nq + 1 entries, offs[0] = 0).  Two steps:
+ *   similarity — one C x C float64 matrix per query: the cosine of the stored float32 rows named by rows_host (row ids
+ *     of the index), clamp(a_i . a_j / (||a_i|| ||a_j||), 0, 1) and 0 where a norm is zero (:431-444), whatever the index's
+ *     metric or normalisation; the products are exact in float64, accumulated in one fixed order, so the value depends on
+ *     the two rows alone and equal rows give equal columns.  With sim_host != NULL (the concatenated C_q x C_q blocks,
+ *     float64, row-major) that matrix is taken as given instead: h may then be NULL (the call runs on `device`) and
+ *     rows_host is ignored;
+ *   decision — per query, on that matrix, scores_host (float64) and type_masks_host (uint32, bit t = evidence type t;
+ *     NULL = no types), in the reference's float64 order of operations:
+ *       dedup (:383-401; skipped when p->dedup == 0): in input order, the first kept entry with sim >= similarity_threshold
+ *         either survives, or, when the new score is strictly greater, is removed and the new candidate appended;
+ *       kept <= max_candidates: the kept list as it is (:655); otherwise a stable sort by score descending (:659) and
+ *       p->quota == 0: the first of the sorted list, then greedily the candidate with the largest
+ *         0.7 (1 - mean sim to the selected) + 0.3 min(1, score) (:666-687, :781-805);
+ *       p->quota != 0: round one takes, in sorted order, every candidate with a type below its quota (:698-719); round
+ *         two greedily the largest 0.5 score + 0.3 gain + 0.2 bonus, bonus as :761-779 summed over the candidate's types in
+ *         ascending bit order (:724-754);
+ *       a candidate wins only with a value strictly above -1.0 and strictly above every earlier one: ties go to the
+ *       earlier position of the sorted list, and a step without a winner ends the selection (:684, :753).
+ * Outputs (host): kept / selected: int32 [offs[nq]], query q's entries from offs[q], positions within the query's list, in
+ * kept order / selection order; n_kept / n_selected: int32 [nq]; sel_sim: float64, query q's block starts at the sum of
+ * min(C_r, max_candidates)^2 over r < q and holds the K x K similarities of its K selected candidates, row-major with
+ * row length K (what SemanticDiversityEvaluator.evaluate_diversity, :173-194, sums).  Any output pointer may be NULL.
+ * ANR_EINVAL: a list longer than 1024, a row id outside [0, ntotal), max_candidates < 1, a threshold that is NaN,
+ * offs not ascending from 0, h == NULL without sim_host.  nq == 0 or all lists empty: ANR_OK. */
+typedef struct anr_diversity_params {
+  int32_t max_candidates;
+  int32_t dedup;               /* 0: skip the dedup stage */
+  int32_t quota;               /* 0: plain greedy form, else the evidence-quota form */
+  int32_t reserved;
+  double similarity_threshold;
+  double balance_factor;       /* quota_balance_factor */
+  int32_t quotas[32];          /* quota of evidence type t (0 = none) */
+} anr_diversity_params;
+int anr_index_diversify(anr_index *h, int32_t device, int64_t nq, const int64_t *offs, const int64_t *rows_host,
+                        const double *sim_host, const double *scores_host, const uint32_t *type_masks_host,
+                        const anr_diversity_params *p, int32_t *kept, int32_t *n_kept, int32_t *selected,
+                        int32_t *n_selected, double *sel_sim);
+/* Developer timing of anr_index_diversify (tools/diversity_perf.py; process-wide, not for concurrent callers): enable != 0
+ * makes later calls record HIP events; ms3 (may be NULL) receives the last timed call's milliseconds: [0] the similarity
+ * kernels (or the upload of sim_host), [1] the decision kernel, [2] first copy in to last copy out. */
+int anr_diversify_timing(int32_t enable, float *ms3);
+
 /* tuning / introspection */
 #define ANR_OPT_FORCE_EXACT 1     /* 1: skip the f16 scan, run the dense exact path for every query  */
 #define ANR_OPT_OVERFETCH 2       /* candidates kept per query before the exact re-score (0 = auto)  */
