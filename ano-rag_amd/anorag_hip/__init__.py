@@ -5,4 +5,5 @@ from .ivf_index import IVFIndex  # noqa: F401
 from .graph_index import GraphIndex  # noqa: F401
 from .note_graph import NoteGraph  # noqa: F401
 from .topic_clustering import cluster_labels, dbscan_labels, find_optimal_eps  # noqa: F401
+from .topic_clustering import analyze_clusters, cluster_cohesion, silhouette_samples, silhouette_score  # noqa: F401
 from .diversity import diversify  # noqa: F401

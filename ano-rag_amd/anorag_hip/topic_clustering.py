@@ -11,6 +11,13 @@ on the host: O(N^2 d) for the k-distance curve and again for DBSCAN.  Here both 
 ``hdbscan`` (the reference's default) and ``kmeans`` are not provided: their results are not functions of the data alone
 (tie order in the spanning tree, sklearn's RNG stream); they stay on sklearn.
 
+What the reference does with the labels of ANY of the three algorithms, ``_analyze_clusters`` (:171-215), is a function of
+(rows, labels) alone and is provided: ``analyze_clusters`` returns its ``cluster_info`` dict, ``silhouette_samples`` /
+``silhouette_score`` sklearn's Euclidean silhouette and ``cluster_cohesion`` scipy's cosine ``pdist`` mean and standard
+deviation per cluster — ``anr_index_cluster_quality``: one float64 MFMA Gram of the stored float32 rows walked in label
+order.  The cluster centres are the reference's own host expression.  Not provided: ``_create_topic_pools``
+and the rest of ``cluster_notes`` (string counting), a drop-in ``TopicClustering`` class, other metrics.
+
 Everything here fails loudly when the HIP library is missing; there is no CPU path.
 """
 from __future__ import annotations
@@ -29,6 +36,8 @@ EPS_INFLATION = 1.0 + 2.0 ** -20
 
 STATS_NAMES = ("n_clusters", "n_core", "n_noise", "n_rescored", "tile_walks", "jump_rounds", "list_regrown",
                "n_rescored_in")
+QUALITY_STATS_NAMES = ("n_labels", "n_noise", "silhouette_tiles", "cohesion_tiles", "n_cohesion_clusters",
+                       "scratch_bytes", "mfma_steps_per_tile", "reserved")
 
 
 def _own_index(embeddings, metric: str, device: int) -> FlatIndex:
@@ -138,4 +147,121 @@ def cluster_labels(embeddings, algorithm: str = "dbscan", min_samples: int = 3, 
     return dbscan_labels(emb, eps, min_samples, "cosine", device)
 
 
-__all__ = ["dbscan_labels", "find_optimal_eps", "cluster_labels", "EPS_INFLATION", "STATS_NAMES"]
+def _int32_labels(labels, n: int) -> np.ndarray:
+    lab = np.asarray(labels)
+    if lab.ndim != 1 or lab.shape[0] != n:
+        raise ValueError(f"expected one label per row: {n} rows, labels of shape {lab.shape}")
+    if lab.dtype.kind not in "iu":
+        raise ValueError(f"labels must be integers, got {lab.dtype}")
+    if lab.size and (int(lab.min()) < -2 ** 31 or int(lab.max()) >= 2 ** 31):
+        raise ValueError("labels must fit a 32-bit integer")
+    return np.ascontiguousarray(lab, dtype=np.int32)
+
+
+def cluster_quality(embeddings_or_index, labels, device: int = 0, silhouette: bool = True, cohesion: bool = True,
+                    return_stats: bool = False):
+    """``anr_index_cluster_quality`` as it is: a dict with ``labels`` (the distinct labels, ascending, int64), ``sizes``,
+    and, as asked for, ``samples`` (float64 silhouette of every row) and ``mean``, ``cohesion`` and ``std`` (per distinct
+    label, NaN where not defined).  Given an array, a temporary L2 index is built; a ``FlatIndex`` must be an L2 one that
+    does not normalise its rows."""
+    own = not isinstance(embeddings_or_index, FlatIndex)
+    index = _own_index(embeddings_or_index, "euclidean", device) if own else embeddings_or_index
+    try:
+        if index.metric != METRIC_L2 or index.normalize:
+            raise ValueError("cluster quality is measured on the rows as given: it needs an L2 index without normalisation")
+        n = index.ntotal
+        lab = _int32_labels(labels, n)
+        cap = max(1, int(np.unique(lab).size))
+        out_labels = np.empty((cap,), dtype=np.int32)
+        sizes = np.zeros((cap,), dtype=np.int64)
+        samples = np.zeros((n,), dtype=np.float64) if silhouette else None
+        mean = C.c_double(0.0)
+        coh = np.full((cap,), np.nan) if cohesion else None
+        std = np.full((cap,), np.nan) if cohesion else None
+        n_labels = C.c_int64(0)
+        stats = np.zeros((8,), dtype=np.int64)
+        ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
+        _lib.check(index._lib.anr_index_cluster_quality(
+            index._h, lab.ctypes.data, ptr(samples), C.addressof(mean) if silhouette else None, cap, out_labels.ctypes.data,
+            sizes.ctypes.data, ptr(coh), ptr(std), C.addressof(n_labels), stats.ctypes.data), "anr_index_cluster_quality")
+    finally:
+        if own:
+            index.close()
+    k = int(n_labels.value)
+    out = {"labels": out_labels[:k].astype(np.int64), "sizes": sizes[:k]}
+    if silhouette:
+        out["samples"], out["mean"] = samples, float(mean.value)
+    if cohesion:
+        out["cohesion"], out["std"] = coh[:k], std[:k]
+    if return_stats:
+        out["stats"] = dict(zip(QUALITY_STATS_NAMES, (int(v) for v in stats)))
+    return out
+
+
+def _check_number_of_labels(n_labels: int, n_samples: int) -> None:
+    if not 1 < n_labels < n_samples:  # sklearn.metrics.cluster._unsupervised.check_number_of_labels
+        raise ValueError(f"Number of labels is {n_labels}. Valid values are 2 to n_samples - 1 (inclusive)")
+
+
+def silhouette_samples(embeddings_or_index, labels, device: int = 0) -> np.ndarray:
+    """sklearn's ``silhouette_samples(X, labels, metric='euclidean')``: float64 [N]; every distinct label value is a
+    cluster (-1 too, as in the reference's call).  Raises ``ValueError`` where sklearn does: a number of distinct labels
+    outside 2 .. N - 1."""
+    q = cluster_quality(embeddings_or_index, labels, device, cohesion=False)
+    _check_number_of_labels(int(q["labels"].size), int(q["samples"].size))
+    return q["samples"]
+
+
+def silhouette_score(embeddings_or_index, labels, device: int = 0) -> float:
+    """sklearn's ``silhouette_score(X, labels)`` (Euclidean): the mean of ``silhouette_samples``, summed on the device in
+    one fixed order."""
+    q = cluster_quality(embeddings_or_index, labels, device, cohesion=False)
+    _check_number_of_labels(int(q["labels"].size), int(q["samples"].size))
+    return q["mean"]
+
+
+def cluster_cohesion(embeddings_or_index, labels, device: int = 0) -> dict:
+    """``{label: {'cohesion', 'std'}}`` for every label >= 0 with at least two rows: ``np.mean`` and ``np.std`` of scipy's
+    ``pdist(rows_of_the_label, metric='cosine')`` (:197-203).  A zero row makes both values of its cluster NaN, as scipy's
+    do."""
+    q = cluster_quality(embeddings_or_index, labels, device, silhouette=False)
+    return {int(lab): {"cohesion": float(c), "std": float(s)}
+            for lab, m, c, s in zip(q["labels"], q["sizes"], q["cohesion"], q["std"]) if lab >= 0 and m > 1}
+
+
+def analyze_clusters(embeddings, labels, device: int = 0) -> dict:
+    """The reference's ``TopicClustering._analyze_clusters(cluster_labels, embeddings)`` (:171-215): its ``cluster_info``
+    dict, same keys, nesting and value types — ``n_clusters``, ``n_noise``, ``cluster_sizes``, ``cluster_centers``,
+    ``cluster_quality`` (clusters of two rows or more) and ``silhouette_score``; noise (-1) has no size, centre or quality.
+    The two O(N^2 d) measures are one ``anr_index_cluster_quality`` call on a temporary L2 index of the float32 rows.
+    ``cluster_centers`` stay on the host: the reference's own expression ``np.mean(embeddings[mask], axis=0).tolist()`` on
+    the float32 rows, O(N d) and bit-identical by construction.  ``silhouette_score`` is 0.0 where the reference's is:
+    unless ``n_clusters > 1 and N > n_clusters``, and where sklearn raises (distinct labels, noise included, outside
+    2 .. N - 1), which the reference's ``except`` turns into 0.0."""
+    emb = np.ascontiguousarray(embeddings, dtype=np.float32)
+    if emb.ndim != 2:
+        raise ValueError(f"expected an [N, d] array of embeddings, got shape {emb.shape}")
+    cluster_labels = np.asarray(labels)
+    _int32_labels(cluster_labels, emb.shape[0])
+    unique_labels = np.unique(cluster_labels)
+    n_clusters = len(unique_labels[unique_labels >= 0])
+    info = {"n_clusters": n_clusters, "n_noise": np.sum(cluster_labels == -1), "cluster_sizes": {}, "cluster_centers": {},
+            "cluster_quality": {}}
+    q = cluster_quality(emb, cluster_labels, device) if emb.shape[0] else None
+    for label in unique_labels:
+        if label == -1:
+            continue
+        mask = cluster_labels == label
+        info["cluster_sizes"][label] = int(np.sum(mask))
+        info["cluster_centers"][label] = np.mean(emb[mask], axis=0).tolist()
+        if info["cluster_sizes"][label] > 1:
+            at = int(np.searchsorted(q["labels"], int(label)))
+            info["cluster_quality"][label] = {"cohesion": float(q["cohesion"][at]), "std": float(q["std"][at])}
+    info["silhouette_score"] = 0.0
+    if n_clusters > 1 and len(emb) > n_clusters and 1 < len(unique_labels) < len(emb):
+        info["silhouette_score"] = float(q["mean"])
+    return info
+
+
+__all__ = ["dbscan_labels", "find_optimal_eps", "cluster_labels", "EPS_INFLATION", "STATS_NAMES", "analyze_clusters",
+           "silhouette_samples", "silhouette_score", "cluster_cohesion", "cluster_quality", "QUALITY_STATS_NAMES"]

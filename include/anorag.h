@@ -192,6 +192,36 @@ int anr_index_diversify(anr_index *h, int32_t device, int64_t nq, const int64_t 
  * kernels (or the upload of sim_host), [1] the decision kernel, [2] first copy in to last copy out. */
 int anr_diversify_timing(int32_t enable, float *ms3);
 
+/* Cluster quality of a labelling of the stored rows: the two measures of TopicClustering._analyze_clusters
+ * (doc/clustering.py:171-215), which cluster_notes (:20-46) runs after every clustering.  L2 index without normalisation
+ * only (ANR_EINVAL otherwise): the float32 rows are used exactly as stored.  Everything comes from one float64 Gram
+ * G = X X^T (f64 MFMA, float32 operands widened, one fixed k-order, squared norms from its own diagonal):
+ *   silhouette (:206-213, sklearn.metrics.silhouette_samples, metric euclidean) — D_ij = sqrt(max(G_ii + G_jj - 2 G_ij, 0)),
+ *     a_i the mean distance to the other rows of i's label, b_i the smallest mean distance to the rows of another label,
+ *     s_i = (b_i - a_i) / max(a_i, b_i); every distinct label value is a cluster, the noise label -1 included, as in the
+ *     reference's call; s_i = 0 for a label of one row, for 0 / 0, and when there is no other label.  Samples are produced
+ *     for any labelling: whether the reference would report 0.0 instead (fewer than 2 clusters, or a number of distinct
+ *     labels outside 2 .. ntotal - 1, where sklearn raises) is the caller's decision;
+ *   cohesion (:197-203, scipy pdist cosine) — per label >= 0 with at least two rows, the mean and the population standard
+ *     deviation (ddof = 0, taken against the finished mean in a second pass) of 1 - G_ij / (sqrt(G_ii) sqrt(G_jj)) over its
+ *     pairs i < j, the cosine clipped to [-1, 1] as scipy does; a pair with a zero row is NaN and makes both values NaN.
+ * Identical rows are at distance exactly 0.  No floating-point atomics: every output is one fixed sequence of operations, two
+ * calls are bit-equal.  Memory beyond the index is O(ntotal) plus 8 bytes per 64 x 64 tile of a cluster's pairs.
+ * labels_host: int32 [ntotal], any values.  Outputs (host; any pointer may be NULL): sil_samples float64 [ntotal] in row
+ * order; sil_mean their mean; labels_out int32 / sizes int64 / cohesion / cohesion_std float64 [label_cap]: the distinct
+ * labels ascending, their sizes and the two cohesion values (NaN where not defined: label < 0 or one row); n_labels: the number
+ * of distinct labels.  stats (8 words, may be NULL): [0] distinct labels, [1] rows labelled -1, [2] 64 x 64 tiles of the
+ * silhouette walk, [3] tiles of one cohesion pass, [4] clusters with a cohesion, [5] bytes of scratch held on the handle,
+ * [6] MFMA steps per tile, [7] 0.  ANR_EINVAL: labels_host NULL; label_cap smaller than the number of distinct labels
+ * while a per-label output is asked for (*n_labels then holds the count needed).  ntotal == 0: ANR_OK, nothing written. */
+int anr_index_cluster_quality(anr_index *h, const int32_t *labels_host, double *sil_samples, double *sil_mean,
+                              int64_t label_cap, int32_t *labels_out, int64_t *sizes, double *cohesion, double *cohesion_std,
+                              int64_t *n_labels, int64_t *stats);
+/* Developer timing of anr_index_cluster_quality (tools/cluster_quality_perf.py; process-wide, not for concurrent callers):
+ * enable != 0 makes later calls record HIP events; ms3 (may be NULL) receives the last timed call's milliseconds: [0] sort,
+ * norms, silhouette walk and mean, [1] the cohesion passes, [2] first copy in to last copy out. */
+int anr_cluster_quality_timing(int32_t enable, float *ms3);
+
 /* tuning / introspection */
 #define ANR_OPT_FORCE_EXACT 1     /* 1: skip the f16 scan, run the dense exact path for every query  */
 #define ANR_OPT_OVERFETCH 2       /* candidates kept per query before the exact re-score (0 = auto)  */
