@@ -7,3 +7,5 @@ from .note_graph import NoteGraph  # noqa: F401
 from .topic_clustering import cluster_labels, dbscan_labels, find_optimal_eps  # noqa: F401
 from .topic_clustering import analyze_clusters, cluster_cohesion, silhouette_samples, silhouette_score  # noqa: F401
 from .diversity import diversify  # noqa: F401
+from . import graph_quality  # noqa: F401
+from .graph_quality import compute_metrics  # noqa: F401

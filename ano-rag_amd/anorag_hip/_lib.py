@@ -35,6 +35,7 @@ OPT_SCAN_BITS = 14
 BATCH_LOG_FIELDS = 14
 ANR_ENOCONV = -5
 NOTEGRAPH_OPT_MAX_SLOTS = 1
+NOTEGRAPH_OPT_BFS_WORDS = 2
 
 
 class AnoragError(RuntimeError):
@@ -263,6 +264,9 @@ SIGNATURES = {
     "anr_notegraph_rows_to_array_dev": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.c_void_p]),
     "anr_notegraph_set_option": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64]),
+    "anr_notegraph_components": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    "anr_notegraph_hop_histogram": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                              C.POINTER(C.c_int64), C.c_void_p]),
 }
 
 _lib = None

@@ -5,6 +5,9 @@
 * ``NoteGraph.retrieve`` / ``graph_retrieve`` replace ``GraphRetriever.retrieve`` (graph/graph_retriever.py:61-92): per
   seed a shortest-path search bounded by a DISTANCE cutoff (``k_hop``), merged in seed order, scored
   ``(centrality / (dist + 1e-5)) * importance`` and sorted best first — for a batch of seed lists at once.
+* ``NoteGraph.components`` / ``hop_histogram`` / ``quality_metrics`` replace ``compute_metrics``
+  (graph/graph_quality.py:5-46): connected components and the average shortest path length of the largest one, from
+  integer counts, equal to the reference's dict in every value.
 * ``NoteGraph.retrieve_device`` leaves the rows on the device; ``NoteGraph.to_array`` turns them into the NaN-filled
   ``DeviceArray`` that ``fuse_dense`` takes as its ``graph`` source (INTEGRATION.md).
 
@@ -85,6 +88,68 @@ class NoteGraph:
         """bound the (query, seed) searches in flight (0 = sized from free device memory); results do not depend on it"""
         _lib.check(self._lib.anr_notegraph_set_option(self._h, _lib.NOTEGRAPH_OPT_MAX_SLOTS, int(slots)),
                    "anr_notegraph_set_option")
+
+    # ---- graph quality (graph/graph_quality.py) ----
+    def set_bfs_words(self, words: int) -> None:
+        """64-bit words per node and pass of ``hop_histogram`` (1, 2, 4, 8, 16; 0 = default): a pass walks 64 * words
+        sources; results do not depend on it"""
+        _lib.check(self._lib.anr_notegraph_set_option(self._h, _lib.NOTEGRAPH_OPT_BFS_WORDS, int(words)),
+                   "anr_notegraph_set_option")
+
+    def components(self) -> Tuple[np.ndarray, List[int]]:
+        """(labels int64 [n], sizes): labels[v] = the smallest node index of v's component; sizes in the order
+        ``nx.connected_components`` yields the components (by first node = ascending label)"""
+        lab = np.empty(self.n, dtype=np.int32)
+        nc = C.c_int64(0)
+        _lib.check(self._lib.anr_notegraph_components(self._h, lab.ctypes.data, C.byref(nc)), "anr_notegraph_components")
+        labels = lab.astype(np.int64)
+        roots = np.flatnonzero(labels == np.arange(self.n))
+        if len(roots) != nc.value:
+            raise _lib.AnoragError(f"components: {nc.value} roots counted on the device, {len(roots)} in the labels")
+        sizes = np.bincount(labels, minlength=self.n)[roots]
+        return labels, [int(s) for s in sizes]
+
+    def hop_histogram(self, sources=None) -> np.ndarray:
+        """counts[l] = the (source, node) pairs at hop distance l (int64; counts[0] = the sources); ``sources`` = node
+        indices, default all nodes.  ``last_bfs_stats``: sources per pass, passes, levels walked, scratch bytes, words,
+        microseconds by HIP events."""
+        if sources is None:
+            ns, ptr, src = self.n, None, None
+        else:
+            src = np.ascontiguousarray(sources, dtype=np.int64).reshape(-1)
+            ns, ptr = len(src), src.ctypes.data
+            if ns == 0:  # no pairs to count (and no pointer to tell from "all nodes")
+                return np.zeros(0, dtype=np.int64)
+        counts = np.zeros(max(self.n, 1), dtype=np.int64)
+        nl = C.c_int64(0)
+        stats = np.zeros(8, dtype=np.int64)
+        _lib.check(self._lib.anr_notegraph_hop_histogram(self._h, ns, ptr, len(counts), counts.ctypes.data, C.byref(nl),
+                                                         stats.ctypes.data), "anr_notegraph_hop_histogram")
+        self.last_bfs_stats = dict(sources_per_pass=int(stats[0]), passes=int(stats[1]), levels=int(stats[2]),
+                                   scratch_bytes=int(stats[3]), words=int(stats[4]), sources=int(stats[5]),
+                                   event_us=int(stats[6]))
+        return counts[:nl.value].copy()
+
+    def quality_metrics(self, self_loops: int = 0) -> Dict[str, Any]:
+        """compute_metrics(G) of graph/graph_quality.py for this graph: the same keys in the same order, floats for the
+        three counts, ``component_sizes`` a list of ints.  ``self_loops``: self-loops the nx.Graph has and this graph
+        cannot hold; G.degree() counts each twice."""
+        labels, sizes = self.components()
+        largest = max(sizes)
+        root = np.flatnonzero(labels == np.arange(self.n))[sizes.index(largest)]  # the first of the largest
+        if largest > 1:
+            counts = self.hop_histogram(np.flatnonzero(labels == root))
+            total = sum(l * int(c) for l, c in enumerate(counts))
+            aspl = total / (largest * (largest - 1))  # nx.average_shortest_path_length's own last line
+        else:
+            aspl = 0.0
+        return {
+            "average_degree": (2 * self.n_edges + 2 * int(self_loops)) / float(self.n),
+            "num_components": float(len(sizes)),
+            "largest_component_size": float(largest),
+            "average_shortest_path_length": aspl,
+            "component_sizes": sizes,
+        }
 
     # ---- query time ----
     @staticmethod

@@ -16,6 +16,13 @@
 //           per-query owner row (integer atomicMin of the seed position), and the query's nodes are ordered by four stable
 //           radix sorts (id, dist, seed position, score descending).  Slots and queries are reset from their touched /
 //           result lists, never by an n-wide fill.
+//   quality (graph/graph_quality.py:5-46).  Hop counts only: the weights are not read.  Components: every
+//           node ends with the smallest node index of its component, by rounds of (hook: integer atomicMin of the smaller
+//           label into the larger label's node, over the CSR entries; flatten: every node follows its labels to a root)
+//           until a hook finds no edge between two labels.  Hop histogram: a pass walks 64 * W sources at once; a node has W
+//           64-bit words in each of seen / frontier / next, bit j = source j of the pass, and a level is a pull over the
+//           CSR (next[v] = OR of frontier[u] over the row & ~seen[v]) whose popcount is the number of (source, node) pairs
+//           at that hop.  Only integers: the result does not depend on the schedule, the grid or W.
 //
 // This file is compiled with -ffp-contract=off (csrc/Makefile): `a * b + c` is two roundings, as in the reference.
 #include <algorithm>
@@ -332,6 +339,131 @@ __global__ __launch_bounds__(256) void k_ng_scatter_rows(const uint32_t *ids, co
   if (id < n) out[q * n + id] = scores[q * cap + i];
 }
 
+// ---- graph quality: components ---------------------------------------------------------------------------------------
+constexpr int kNgBfsWords = 16;  // default words per node and pass: a node's row of words is one 128-byte line (§5i)
+
+__global__ __launch_bounds__(256) void k_ng_iota_i32(int32_t *x, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) x[i] = (int32_t)i;
+}
+
+// Every label is a node of the same component with label[x] <= x, before and after.  An edge between two labels lowers
+// the larger label's node to the smaller label; each undirected edge is looked at from its larger end.
+__global__ __launch_bounds__(256) void k_ng_cc_hook(const int64_t *rowptr, const int32_t *nbr, int64_t n, int32_t *label,
+                                                    int *changed) {
+  const int64_t u = ((int64_t)blockIdx.x * 256 + threadIdx.x) / kNgLanes;
+  const int lane = threadIdx.x % kNgLanes;
+  if (u >= n) return;
+  const int32_t lu = __atomic_load_n(&label[u], __ATOMIC_RELAXED);
+  bool any = false;
+  for (int64_t e = rowptr[u] + lane; e < rowptr[u + 1]; e += kNgLanes) {
+    const int32_t v = nbr[e];
+    if (v >= u) continue;
+    const int32_t lv = __atomic_load_n(&label[v], __ATOMIC_RELAXED);
+    if (lu == lv) continue;
+    atomicMin(&label[lu > lv ? lu : lv], lu > lv ? lv : lu);
+    any = true;
+  }
+  if (any) *changed = 1;
+}
+
+// label[v] = the root its labels lead to.  Labels only fall and only thread v stores label[v], so a walk that meets
+// another thread's store still ends at a root of v's component.
+__global__ __launch_bounds__(256) void k_ng_cc_flatten(int32_t *label, int64_t n) {
+  const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (v >= n) return;
+  int32_t l = __atomic_load_n(&label[v], __ATOMIC_RELAXED);
+  for (;;) {
+    const int32_t ll = __atomic_load_n(&label[l], __ATOMIC_RELAXED);
+    if (ll == l) break;
+    l = ll;
+  }
+  __atomic_store_n(&label[v], l, __ATOMIC_RELAXED);
+}
+
+// the sum of a workgroup's per-thread counts, valid in thread 0
+__device__ __forceinline__ unsigned ng_count_block(unsigned c, unsigned *sh) {
+  for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = c;
+  __syncthreads();
+  return sh[0] + sh[1] + sh[2] + sh[3];
+}
+
+__global__ __launch_bounds__(256) void k_ng_cc_roots(const int32_t *label, int64_t n, u64 *count) {
+  __shared__ unsigned sh[kNgThreads / 64];
+  const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const unsigned c = ng_count_block(v < n && label[v] == (int32_t)v ? 1u : 0u, sh);
+  if (threadIdx.x == 0 && c) atomicAdd(count, (u64)c);
+}
+
+// ---- graph quality: hop histogram ------------------------------------------------------------------------------------
+struct NgBfs {
+  const int64_t *rowptr;
+  const int32_t *nbr;
+  const int32_t *src;  // the pass's sources, or NULL: source j is node base + j
+  int64_t n, base, nbits;  // nbits: sources of this pass, <= 64 * W
+  int W, wshift;       // words per node, log2
+  const u64 *fin;      // [n][W] frontier
+  u64 *fout, *seen;    // [n][W]
+  u64 *cnt;            // [2] pair counts of this level (slot) and of the next (zeroed here)
+  int slot;
+};
+
+// seen = frontier = the sources' own bits (both zero before).  Two sources of one word that are the same node store the
+// same word: each ORs in the bits of every source of its word that names its node.
+__global__ __launch_bounds__(256) void k_ng_bfs_seed(NgBfs p, u64 *fin) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= p.nbits) return;
+  const int64_t s = p.src ? (int64_t)p.src[j] : p.base + j;
+  u64 bits = 1ull << (j & 63);
+  if (p.src) {
+    const int64_t g0 = j & ~63ll, g1 = g0 + 64 < p.nbits ? g0 + 64 : p.nbits;
+    for (int64_t k = g0; k < g1; ++k)
+      if (p.src[k] == (int32_t)s) bits |= 1ull << (k - g0);
+  }
+  const int64_t i = s * p.W + (j >> 6);
+  p.seen[i] = bits;
+  fin[i] = bits;
+}
+
+// One level, pull form.  Lane w of a node's W adjacent lanes owns word w: a neighbour's row of words is one contiguous
+// load of the group.  A word whose pass bits are all seen can gain nothing and skips its row.
+__global__ __launch_bounds__(256) void k_ng_bfs_level(NgBfs p) {
+  __shared__ unsigned sh[kNgThreads / 64];
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;  // = v * W + w
+  const int64_t v = i >> p.wshift;
+  const int w = (int)(i & (p.W - 1));
+  unsigned c = 0;
+  if (v < p.n) {
+    const int64_t lo = (int64_t)w * 64;
+    const u64 full = p.nbits >= lo + 64 ? ~0ull : p.nbits > lo ? (1ull << (p.nbits - lo)) - 1 : 0ull;
+    const u64 s = p.seen[i];
+    u64 nx = 0;
+    if (~s & full) {
+      u64 a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+      int64_t e = p.rowptr[v];
+      const int64_t end = p.rowptr[v + 1];
+      for (; e + 4 <= end; e += 4) {
+        const int64_t u0 = p.nbr[e], u1 = p.nbr[e + 1], u2 = p.nbr[e + 2], u3 = p.nbr[e + 3];
+        a0 |= p.fin[(u0 << p.wshift) + w];
+        a1 |= p.fin[(u1 << p.wshift) + w];
+        a2 |= p.fin[(u2 << p.wshift) + w];
+        a3 |= p.fin[(u3 << p.wshift) + w];
+      }
+      for (; e < end; ++e) a0 |= p.fin[((int64_t)p.nbr[e] << p.wshift) + w];
+      nx = (a0 | a1 | a2 | a3) & ~s;
+      if (nx) p.seen[i] = s | nx;
+    }
+    p.fout[i] = nx;
+    c = (unsigned)__popcll(nx);
+  }
+  c = ng_count_block(c, sh);
+  if (threadIdx.x == 0) {
+    if (c) atomicAdd(&p.cnt[p.slot], (u64)c);
+    if (blockIdx.x == 0) p.cnt[p.slot ^ 1] = 0ull;  // the next level's counter: no launch in flight uses it
+  }
+}
+
 }  // namespace anr
 
 using namespace anr;
@@ -363,6 +495,16 @@ struct anr_notegraph {
   int64_t *o_ids = nullptr;  // [ws_q][ws_cap] staging of the host outputs
   double *o_dist = nullptr, *o_score = nullptr;
   int32_t *o_pos = nullptr;
+  // graph quality workspace (components, hop histogram): its own buffers, grown when a call needs more, freed at destroy;
+  // it shares nothing with the retrieve workspace above
+  int64_t bfs_words = 0;      // ANR_NOTEGRAPH_OPT_BFS_WORDS, 0 = kNgBfsWords
+  int64_t q_state_cap = 0;    // u64 elements of q_state
+  u64 *q_state = nullptr;     // seen, frontier, next: 3 x [n][W]
+  int64_t q_src_cap = 0;
+  int32_t *q_src = nullptr;   // the explicit sources of a call
+  int32_t *q_label = nullptr;  // [n]
+  u64 *q_cnt = nullptr;       // [2] level counters, [2] root count
+  int *q_flag = nullptr;
 };
 
 namespace {
@@ -391,6 +533,17 @@ void free_workspace(anr_notegraph *h) {
   h->ws_slots = h->ws_q = 0;
   h->ws_cap = 0;
   h->ws_slots_limited = h->ws_q_limited = false;
+}
+
+void free_quality_workspace(anr_notegraph *h) {
+  g_free(h->q_state); g_free(h->q_src); g_free(h->q_label); g_free(h->q_cnt); g_free(h->q_flag);
+  h->q_state_cap = h->q_src_cap = 0;
+}
+
+int ensure_quality_small(anr_notegraph *h) {
+  if (!h->q_cnt) ANR_TRY(g_alloc(&h->q_cnt, 4));
+  if (!h->q_flag) ANR_TRY(g_alloc(&h->q_flag, 1));
+  return ANR_OK;
 }
 
 // bytes per (query, seed) slot, per query of a batch, and shared by all
@@ -671,6 +824,7 @@ int anr_notegraph_destroy(anr_notegraph *h) {
   DeviceGuard g(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   free_workspace(h);
+  free_quality_workspace(h);
   g_free(h->rowptr); g_free(h->nbr); g_free(h->wt); g_free(h->cent); g_free(h->imp);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
@@ -809,6 +963,136 @@ int anr_notegraph_rows_to_array_dev(anr_notegraph *h, int64_t nq, int32_t cap, c
   return ANR_OK;
 }
 
+int anr_notegraph_components(anr_notegraph *h, int32_t *labels_host, int64_t *n_components) {
+  if (!h || !labels_host) return fail(ANR_EINVAL, "bad argument");
+  std::lock_guard<std::mutex> lk(h->mu);
+  DeviceGuard g(h->device);
+  hipStream_t st = h->stream;
+  const int64_t n = h->n;
+  ANR_TRY(ensure_quality_small(h));
+  if (!h->q_label) ANR_TRY(g_alloc(&h->q_label, n));
+  hipLaunchKernelGGL(k_ng_iota_i32, dim3(blocks(n)), dim3(256), 0, st, h->q_label, n);
+  for (int changed = h->m > 0; changed;) {
+    ANR_HIP(hipMemsetAsync(h->q_flag, 0, sizeof(int), st));
+    hipLaunchKernelGGL(k_ng_cc_hook, dim3(blocks(n * kNgLanes)), dim3(256), 0, st, h->rowptr, h->nbr, n, h->q_label,
+                       h->q_flag);
+    hipLaunchKernelGGL(k_ng_cc_flatten, dim3(blocks(n)), dim3(256), 0, st, h->q_label, n);
+    ANR_HIP(hipGetLastError());
+    ANR_HIP(hipMemcpyAsync(&changed, h->q_flag, sizeof(int), hipMemcpyDeviceToHost, st));
+    ANR_HIP(hipStreamSynchronize(st));
+  }
+  u64 roots = 0;
+  ANR_HIP(hipMemsetAsync(h->q_cnt + 2, 0, sizeof(u64), st));
+  hipLaunchKernelGGL(k_ng_cc_roots, dim3(blocks(n)), dim3(256), 0, st, h->q_label, n, h->q_cnt + 2);
+  ANR_HIP(hipGetLastError());
+  ANR_HIP(hipMemcpyAsync(&roots, h->q_cnt + 2, sizeof(u64), hipMemcpyDeviceToHost, st));
+  ANR_HIP(hipMemcpyAsync(labels_host, h->q_label, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  ANR_HIP(hipStreamSynchronize(st));
+  if (n_components) *n_components = (int64_t)roots;
+  return ANR_OK;
+}
+
+int anr_notegraph_hop_histogram(anr_notegraph *h, int64_t n_sources, const int64_t *sources, int64_t cap,
+                                int64_t *counts_host, int64_t *n_levels, int64_t *stats8) {
+  if (!h || cap < 0 || (cap > 0 && !counts_host)) return fail(ANR_EINVAL, "bad argument");
+  if (n_levels) *n_levels = 0;
+  const int64_t n = h->n;
+  if (!sources) n_sources = n;
+  if (n_sources < 0) return fail(ANR_EINVAL, "n_sources must be >= 0");
+  std::vector<int32_t> src32;
+  if (sources) {
+    src32.resize((size_t)n_sources);
+    for (int64_t j = 0; j < n_sources; ++j) {
+      if (sources[j] < 0 || sources[j] >= n)
+        return fail(ANR_EINVAL, "source %lld: node %lld out of range", (long long)j, (long long)sources[j]);
+      src32[(size_t)j] = (int32_t)sources[j];
+    }
+  }
+  std::lock_guard<std::mutex> lk(h->mu);
+  DeviceGuard g(h->device);
+  hipStream_t st = h->stream;
+  ANR_TRY(ensure_quality_small(h));
+  // words per node: the option or the default, halved while three state arrays do not fit half of the free memory
+  int64_t W = h->bfs_words > 0 ? h->bfs_words : kNgBfsWords;
+  if (h->q_state_cap < 3 * n * W) {
+    g_free(h->q_state);
+    h->q_state_cap = 0;
+    size_t free_b = 0, total_b = 0;
+    ANR_HIP(hipMemGetInfo(&free_b, &total_b));
+    while (W > 1 && (size_t)(3 * n * W) * 8 > free_b / 2) W /= 2;
+    ANR_TRY(g_alloc(&h->q_state, 3 * n * W));
+    h->q_state_cap = 3 * n * W;
+  }
+  if (sources && h->q_src_cap < n_sources) {
+    g_free(h->q_src);
+    h->q_src_cap = 0;
+    ANR_TRY(g_alloc(&h->q_src, n_sources));
+    h->q_src_cap = n_sources;
+  }
+  if (sources && n_sources > 0)
+    ANR_HIP(hipMemcpyAsync(h->q_src, src32.data(), (size_t)n_sources * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  const int64_t B = 64 * W, words = n * W;
+  NgBfs p{};
+  p.rowptr = h->rowptr; p.nbr = h->nbr; p.n = n; p.W = (int)W; p.cnt = h->q_cnt;
+  while ((1 << p.wshift) < W) p.wshift += 1;
+  p.seen = h->q_state;
+  u64 *fa = h->q_state + words, *fb = h->q_state + 2 * words;
+  std::vector<int64_t> counts;
+  if (n_sources > 0) counts.push_back(n_sources);
+  int64_t passes = 0, walked = 0;
+  int slot = 0;
+  struct Events {  // the call's span on the stream, for stats8[6]
+    hipEvent_t a = nullptr, b = nullptr;
+    ~Events() {
+      if (a) (void)hipEventDestroy(a);
+      if (b) (void)hipEventDestroy(b);
+    }
+  } ev;
+  if (stats8) {
+    ANR_HIP(hipEventCreate(&ev.a));
+    ANR_HIP(hipEventCreate(&ev.b));
+    ANR_HIP(hipEventRecord(ev.a, st));
+  }
+  ANR_HIP(hipMemsetAsync(h->q_cnt, 0, 2 * sizeof(u64), st));
+  for (int64_t s0 = 0; s0 < n_sources; s0 += B, ++passes) {
+    p.base = s0;
+    p.nbits = std::min<int64_t>(B, n_sources - s0);
+    p.src = sources ? h->q_src + s0 : nullptr;
+    ANR_HIP(hipMemsetAsync(p.seen, 0, (size_t)words * 8, st));
+    ANR_HIP(hipMemsetAsync(fa, 0, (size_t)words * 8, st));
+    hipLaunchKernelGGL(k_ng_bfs_seed, dim3(blocks(p.nbits)), dim3(256), 0, st, p, fa);
+    u64 *fin = fa, *fout = fb;
+    for (int64_t level = 1;; ++level) {
+      p.fin = fin; p.fout = fout; p.slot = slot;
+      hipLaunchKernelGGL(k_ng_bfs_level, dim3(blocks(words)), dim3(256), 0, st, p);
+      ANR_HIP(hipGetLastError());
+      u64 added = 0;
+      ANR_HIP(hipMemcpyAsync(&added, h->q_cnt + slot, sizeof(u64), hipMemcpyDeviceToHost, st));
+      ANR_HIP(hipStreamSynchronize(st));
+      slot ^= 1;
+      walked += 1;
+      if (added == 0) break;
+      if ((int64_t)counts.size() <= level) counts.resize((size_t)level + 1, 0);
+      counts[(size_t)level] += (int64_t)added;
+      std::swap(fin, fout);
+    }
+  }
+  if (stats8) {
+    float ms = 0.0f;
+    ANR_HIP(hipEventRecord(ev.b, st));
+    ANR_HIP(hipEventSynchronize(ev.b));
+    ANR_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
+    const int64_t st8[8] = {B, passes, walked, 3 * words * 8 + (sources ? n_sources * 4 : 0), W, n_sources,
+                            (int64_t)((double)ms * 1000.0), 0};
+    std::copy(st8, st8 + 8, stats8);
+  }
+  if (n_levels) *n_levels = (int64_t)counts.size();
+  if ((int64_t)counts.size() > cap)
+    return fail(ANR_EINVAL, "hop histogram: %lld levels do not fit cap = %lld", (long long)counts.size(), (long long)cap);
+  for (int64_t l = 0; l < cap; ++l) counts_host[l] = l < (int64_t)counts.size() ? counts[(size_t)l] : 0;
+  return ANR_OK;
+}
+
 int anr_notegraph_set_option(anr_notegraph *h, int32_t option, int64_t value) {
   if (!h) return fail(ANR_EINVAL, "null handle");
   std::lock_guard<std::mutex> lk(h->mu);
@@ -818,6 +1102,16 @@ int anr_notegraph_set_option(anr_notegraph *h, int32_t option, int64_t value) {
     (void)hipStreamSynchronize(h->stream);
     free_workspace(h);  // the next retrieve sizes it under the new bound
     h->max_slots = value;
+    return ANR_OK;
+  }
+  if (option == ANR_NOTEGRAPH_OPT_BFS_WORDS) {
+    if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8 && value != 16)
+      return fail(ANR_EINVAL, "BFS words per node must be 0 (default), 1, 2, 4, 8 or 16");
+    DeviceGuard g(h->device);
+    (void)hipStreamSynchronize(h->stream);
+    g_free(h->q_state);  // the next hop histogram sizes it for the new width
+    h->q_state_cap = 0;
+    h->bfs_words = value;
     return ANR_OK;
   }
   return fail(ANR_EINVAL, "unknown note graph option %d", (int)option);

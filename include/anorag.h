@@ -694,7 +694,33 @@ int anr_notegraph_rows_to_array_dev(anr_notegraph *h, int64_t nq, int32_t cap, c
 /* options: 1 = ANR_NOTEGRAPH_OPT_MAX_SLOTS — an upper bound on the (query, seed) searches in flight at a time (0 = sized
  * from free device memory; tests force 1 to walk the sub-batching).  Results never depend on it. */
 #define ANR_NOTEGRAPH_OPT_MAX_SLOTS 1
+/* 2 = ANR_NOTEGRAPH_OPT_BFS_WORDS — the 64-bit words per node and pass of anr_notegraph_hop_histogram: 1, 2, 4, 8 or 16
+ * (0 = the default, 16); a pass walks 64 * words sources.  Tests force 1 and 2 to walk many passes on small graphs.
+ * Results never depend on it. */
+#define ANR_NOTEGRAPH_OPT_BFS_WORDS 2
 int anr_notegraph_set_option(anr_notegraph *h, int32_t option, int64_t value);
+
+/* Graph quality (opt-in): the integers behind compute_metrics (graph/graph_quality.py:5-46), which
+ * GraphBuilder.build_graph_with_metrics runs on every graph (graph/graph_builder.py:39-49).  Hop counts on the handle's
+ * symmetric CSR; the weights are not read (nx.average_shortest_path_length is called with weight=None).  Layout, the words
+ * per pass and the bytes per level: DESIGN.md §5i.
+ *
+ * nx.connected_components (graph_quality.py:33,37): labels_host[v] = the smallest node index of v's component, found by
+ * integer atomicMin hooking and pointer jumping until a round changes nothing; *n_components (may be NULL) = the number
+ * of distinct labels.  Ascending label is the order in which networkx yields the components (by first node). */
+int anr_notegraph_components(anr_notegraph *h, int32_t *labels_host /*[n]*/, int64_t *n_components);
+/* The sum nx.average_shortest_path_length forms (graph_quality.py:40), kept apart by hop count: counts_host[l] = the
+ * number of (source, node) pairs at hop distance l, over the n_sources nodes sources[] (NULL = all n nodes, n_sources is
+ * then ignored); counts_host[0] = n_sources; a pair in different components is counted nowhere.  A multi-source
+ * bit-parallel BFS: 64 * words sources per pass, one pull over the CSR per level, integer popcounts added per workgroup.
+ * *n_levels = the entries in use (the largest distance + 1); counts_host has room for cap entries and is zero beyond
+ * *n_levels.  ANR_EINVAL for a source outside [0, n), and when more than cap levels are needed — *n_levels is then the
+ * number needed and counts_host is left alone; cap = n always suffices.
+ * stats8 (may be NULL), int64 [8]: 0 sources per pass, 1 passes, 2 levels walked over all passes (one launch each,
+ * the closing empty level of a pass included), 3 scratch bytes in use, 4 words per node, 5 sources, 6 microseconds between two HIP
+ * events around the call's work on the handle's stream (the host's reading of each level's count lies inside), 7 zero. */
+int anr_notegraph_hop_histogram(anr_notegraph *h, int64_t n_sources, const int64_t *sources, int64_t cap,
+                                int64_t *counts_host, int64_t *n_levels, int64_t *stats8);
 
 #ifdef __cplusplus
 }
