@@ -34,6 +34,7 @@ OPT_STREAM_WAIT = 13
 OPT_SCAN_BITS = 14
 BATCH_LOG_FIELDS = 14
 ANR_ENOCONV = -5
+ANR_EEMPTY = -6
 NOTEGRAPH_OPT_MAX_SLOTS = 1
 NOTEGRAPH_OPT_BFS_WORDS = 2
 
@@ -144,6 +145,8 @@ SIGNATURES = {
     "anr_index_cluster_quality": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "anr_cluster_quality_timing": (C.c_int, [C.c_int32, C.c_void_p]),
+    "anr_index_kmeans": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_double,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "anr_index_set_option": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64]),
     "anr_index_last_stats": (C.c_int, [C.c_void_p, C.POINTER(SearchStats)]),
     "anr_index_reconstruct_scan_image": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p]),

@@ -8,8 +8,15 @@ on the host: O(N^2 d) for the k-distance curve and again for DBSCAN.  Here both 
 * ``dbscan_labels`` is ``anr_index_dbscan``: the MFMA self join's tile walk with the eps pairs consumed where they are
   produced (degree, union and border pass).  The labels are sklearn's, label for label.
 
-``hdbscan`` (the reference's default) and ``kmeans`` are not provided: their results are not functions of the data alone
-(tie order in the spanning tree, sklearn's RNG stream); they stay on sklearn.
+``hdbscan`` (the reference's default) is not provided: its result is not a function of the data alone (tie order in the
+spanning tree); it stays on sklearn, and ``cluster_labels`` keeps refusing it and ``kmeans``.
+
+K-means has names of its own.  The reference fixes ``random_state=42`` and every draw sklearn makes is independent of the
+data, so the host draws them all up front (``kmeans_draws``) and ``anr_index_kmeans`` runs the rest on the stored rows
+(DESIGN.md §5j): ``kmeans_fit`` is ``KMeans(n_clusters, n_init, random_state).fit``, ``find_optimal_k`` the reference's
+``_find_optimal_k`` (:110-147), ``kmeans_topic_labels`` what the ``kmeans`` branch (:80-87) returns and ``fallback_labels``
+what ``_fallback_clustering`` (:101-108) returns.  An input on which a cluster loses all its rows raises
+``EmptyClusterError``: sklearn relocates such a centre in an order that is not defined, so that input stays on sklearn.
 
 What the reference does with the labels of ANY of the three algorithms, ``_analyze_clusters`` (:171-215), is a function of
 (rows, labels) alone and is provided: ``analyze_clusters`` returns its ``cluster_info`` dict, ``silhouette_samples`` /
@@ -36,6 +43,9 @@ EPS_INFLATION = 1.0 + 2.0 ** -20
 
 STATS_NAMES = ("n_clusters", "n_core", "n_noise", "n_rescored", "tile_walks", "jump_rounds", "list_regrown",
                "n_rescored_in")
+KMEANS_STATS_NAMES = ("lloyd_iterations", "assignment_passes", "seeding_steps", "scratch_bytes", "mfma_steps_per_tile",
+                      "emptied_init", "strict_inits", "tol")
+KMEANS_MAX_CLUSTERS = 64
 QUALITY_STATS_NAMES = ("n_labels", "n_noise", "silhouette_tiles", "cohesion_tiles", "n_cohesion_clusters",
                        "scratch_bytes", "mfma_steps_per_tile", "reserved")
 
@@ -145,6 +155,131 @@ def cluster_labels(embeddings, algorithm: str = "dbscan", min_samples: int = 3, 
     finally:
         l2.close()
     return dbscan_labels(emb, eps, min_samples, "cosine", device)
+
+
+class EmptyClusterError(_lib.AnoragError):
+    """A k-means cluster lost all its rows.  sklearn relocates such a centre through an ``argpartition`` whose order is
+    not defined, so the device does not follow it: keep sklearn for this input."""
+
+
+def kmeans_draws(n_samples: int, n_clusters: int, n_init: int, random_state=42):
+    """Every random draw of sklearn's ``KMeans(n_clusters, n_init=n_init, random_state=random_state).fit`` on
+    ``n_samples`` float32 rows, in sklearn's order from one ``np.random.RandomState``: per init the first centre,
+    ``choice(n, p=w / w.sum())`` with ``w`` the float32 unit sample weights, then per further centre one
+    ``uniform(size=2 + int(log(k)))``.  Returns (first_rows int64 [n_init], uniforms float64 [n_init, k - 1, trials])."""
+    rs = random_state if isinstance(random_state, np.random.RandomState) else np.random.RandomState(random_state)
+    trials = 2 + int(np.log(n_clusters))
+    w = np.ones(n_samples, dtype=np.float32)
+    first = np.empty((n_init,), dtype=np.int64)
+    uniforms = np.empty((n_init, n_clusters - 1, trials), dtype=np.float64)
+    for i in range(n_init):
+        first[i] = rs.choice(n_samples, p=w / w.sum())
+        for c in range(n_clusters - 1):
+            uniforms[i, c] = rs.uniform(size=trials)
+    return first, uniforms
+
+
+def kmeans_fit(embeddings_or_index, n_clusters: int, n_init: int, random_state=42, device: int = 0,
+               return_stats: bool = False, max_iter: int = 300, tol: float = 1e-4):
+    """sklearn's ``KMeans(n_clusters, n_init=n_init, random_state=random_state).fit`` of the rows (k-means++, Lloyd):
+    ``(labels int64 [N], centres float64 [k, d], inertia, n_iter)``; ``return_stats=True`` adds a dict
+    (``KMEANS_STATS_NAMES`` and ``best_init``).  Given an array, a temporary L2 index is built; a ``FlatIndex`` must be
+    an L2 one that does not normalise its rows.  ``ValueError`` for k < 2, k > N or k > ``KMEANS_MAX_CLUSTERS``;
+    ``EmptyClusterError`` when a cluster loses all its rows."""
+    k, n_init = int(n_clusters), int(n_init)
+    own = not isinstance(embeddings_or_index, FlatIndex)
+    index = _own_index(embeddings_or_index, "euclidean", device) if own else embeddings_or_index
+    try:
+        if index.metric != METRIC_L2 or index.normalize:
+            raise ValueError("k-means runs on the rows as given: it needs an L2 index without normalisation")
+        n = index.ntotal
+        if k < 2:
+            raise ValueError(f"n_clusters={k}: the device k-means needs at least 2")
+        if k > KMEANS_MAX_CLUSTERS:
+            raise ValueError(f"n_clusters={k} is above the {KMEANS_MAX_CLUSTERS} the device k-means holds")
+        if n < k:
+            raise ValueError(f"n_samples={n} should be >= n_clusters={k}.")
+        if n_init < 1:
+            raise ValueError(f"n_init={n_init} must be at least 1")
+        first, uniforms = kmeans_draws(n, k, n_init, random_state)
+        uniforms = np.ascontiguousarray(uniforms)
+        labels = np.empty((n,), dtype=np.int32)
+        centres = np.empty((k, index.d), dtype=np.float64)
+        inertia, n_iter, best = C.c_double(0.0), C.c_int32(0), C.c_int32(-1)
+        stats = np.zeros((8,), dtype=np.int64)
+        rc = index._lib.anr_index_kmeans(index._h, k, n_init, uniforms.shape[2], first.ctypes.data, uniforms.ctypes.data,
+                                         int(max_iter), C.c_double(float(tol)), labels.ctypes.data, centres.ctypes.data,
+                                         C.addressof(inertia), C.addressof(n_iter), C.addressof(best), stats.ctypes.data)
+        if rc == _lib.ANR_EEMPTY:
+            raise EmptyClusterError(f"anr_index_kmeans failed (code {rc}): {_lib.last_error()}")
+        _lib.check(rc, "anr_index_kmeans")
+    finally:
+        if own:
+            index.close()
+    out = (labels.astype(np.int64), centres, float(inertia.value), int(n_iter.value))
+    if return_stats:
+        st = dict(zip(KMEANS_STATS_NAMES, (int(v) for v in stats)))
+        st["tol"] = float(stats[7:8].view(np.float64)[0])
+        st["best_init"] = int(best.value)
+        return out + (st,)
+    return out
+
+
+def _find_elbow_point(k_values, inertias) -> int:
+    if len(k_values) < 3:  # the reference's _find_elbow_point (:136-147), its own expression
+        return k_values[0] if k_values else 2
+    diffs = np.diff(inertias)
+    second_diffs = np.diff(diffs)
+    elbow_idx = np.argmax(second_diffs) + 1
+    return k_values[elbow_idx]
+
+
+def find_optimal_k(embeddings_or_index, max_k=None, device: int = 0, return_inertias: bool = False):
+    """The reference's ``_find_optimal_k`` (:110-134): ``KMeans(k, random_state=42, n_init=5)`` for k = 2 .. max_k
+    (default ``min(10, N // 5)``), a fresh stream per k, then the elbow of the inertias by the reference's own host
+    expression; 2 when ``max_k < 2`` or fewer than two fits succeed.  The reference's ``except`` ends the loop at the
+    first fit that raises, which for sklearn is k > N; the loop ends there here too.  Every other failure (a k above
+    ``KMEANS_MAX_CLUSTERS``, ``EmptyClusterError``) is raised: sklearn would have gone on.
+    ``return_inertias=True``: ``(k, inertias)``."""
+    own = not isinstance(embeddings_or_index, FlatIndex)
+    index = _own_index(embeddings_or_index, "euclidean", device) if own else embeddings_or_index
+    try:
+        if max_k is None:
+            max_k = min(10, index.ntotal // 5)
+        inertias = []
+        k_range = range(2, max_k + 1)
+        if max_k >= 2:
+            for k in k_range:
+                if k > index.ntotal:
+                    break
+                inertias.append(kmeans_fit(index, k, 5, 42, device)[2])
+    finally:
+        if own:
+            index.close()
+    if max_k < 2 or len(inertias) < 2:
+        optimal_k = 2
+    else:
+        optimal_k = int(_find_elbow_point(list(k_range)[:len(inertias)], inertias))
+    return (optimal_k, inertias) if return_inertias else optimal_k
+
+
+def kmeans_topic_labels(embeddings, device: int = 0) -> np.ndarray:
+    """What ``_cpu_clustering`` returns for ``clustering.algorithm: kmeans`` (:80-87, :99): ``find_optimal_k``, then
+    ``KMeans(optimal_k, random_state=42, n_init=10).fit_predict``.  The rows go to one temporary index once for all
+    fits."""
+    index = _own_index(embeddings, "euclidean", device)
+    try:
+        return kmeans_fit(index, find_optimal_k(index, device=device), 10, 42, device)[0]
+    finally:
+        index.close()
+
+
+def fallback_labels(embeddings, device: int = 0) -> np.ndarray:
+    """What ``_fallback_clustering`` returns (:101-108): ``KMeans(min(8, max(2, N // 10)), random_state=42)`` with
+    sklearn's default ``n_init='auto'``, which is 1 for k-means++ from sklearn 1.4 on (10 before)."""
+    emb = np.ascontiguousarray(embeddings, dtype=np.float32)
+    n_clusters = min(8, max(2, len(emb) // 10))
+    return kmeans_fit(emb, n_clusters, 1, 42, device)[0]
 
 
 def _int32_labels(labels, n: int) -> np.ndarray:
@@ -264,4 +399,6 @@ def analyze_clusters(embeddings, labels, device: int = 0) -> dict:
 
 
 __all__ = ["dbscan_labels", "find_optimal_eps", "cluster_labels", "EPS_INFLATION", "STATS_NAMES", "analyze_clusters",
-           "silhouette_samples", "silhouette_score", "cluster_cohesion", "cluster_quality", "QUALITY_STATS_NAMES"]
+           "silhouette_samples", "silhouette_score", "cluster_cohesion", "cluster_quality", "QUALITY_STATS_NAMES", "kmeans_fit",
+           "kmeans_draws", "find_optimal_k", "kmeans_topic_labels", "fallback_labels", "EmptyClusterError",
+           "KMEANS_STATS_NAMES", "KMEANS_MAX_CLUSTERS"]

@@ -20,6 +20,7 @@
 
 #include "cluster.hpp"
 #include "cluster_quality.hpp"
+#include "kmeans.hpp"
 #include "common.hpp"
 #include "diversity.hpp"
 #include "graph.hpp"
@@ -161,6 +162,7 @@ struct anr_index {
   anr_graph *graph = nullptr;  // graph index on these rows (graph.hip); adds and resets mark it stale
   anr_diversity *diversity = nullptr;  // scratch of anr_index_diversify (diversity.hip)
   anr_cluster_quality *cluster_quality = nullptr;  // scratch of anr_index_cluster_quality (cluster_quality.hip)
+  anr_kmeans *kmeans = nullptr;  // scratch of anr_index_kmeans (kmeans.hip)
 };
 
 namespace {
@@ -1596,6 +1598,7 @@ int anr_index_destroy(anr_index *h) {
   graph_free(h->graph);
   diversity_free(h->diversity);
   cluster_quality_free(h->cluster_quality);
+  kmeans_free(h->kmeans);
   for (auto &e : h->ev_call)
     if (e) (void)hipEventDestroy(e);
   for (hipStream_t s : {h->bstream[0], h->bstream[1], h->bstream[2], h->stream})
@@ -2150,6 +2153,8 @@ anr_graph *&index_graph(anr_index *h) { return h->graph; }
 anr_diversity *&index_diversity(anr_index *h) { return h->diversity; }
 
 anr_cluster_quality *&index_cluster_quality(anr_index *h) { return h->cluster_quality; }
+
+anr_kmeans *&index_kmeans(anr_index *h) { return h->kmeans; }
 
 int index_join_view(anr_index *h, JoinView *out) {
   ANR_TRY(drain(h));

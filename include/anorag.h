@@ -222,6 +222,35 @@ int anr_index_cluster_quality(anr_index *h, const int32_t *labels_host, double *
  * norms, silhouette walk and mean, [1] the cohesion passes, [2] first copy in to last copy out. */
 int anr_cluster_quality_timing(int32_t enable, float *ms3);
 
+/* K-means topic clustering on the stored rows: sklearn's KMeans(n_clusters = k, n_init, random_state).fit as the reference
+ * calls it — the `kmeans` branch of TopicClustering._cpu_clustering (doc/clustering.py:80-87), _fallback_clustering
+ * (:101-108) and the fits of _find_optimal_k (:110-134).  L2 index without normalisation only (ANR_EINVAL otherwise): the
+ * float32 rows are used exactly as stored.  sklearn's random draws do not depend on the data, so the caller makes them
+ * (numpy RandomState, one stream for all inits) and hands them over: first_rows int64 [n_init], the first centre of every
+ * init (`choice`); uniforms float64 [n_init][k - 1][n_local_trials] in [0, 1], the `uniform` draws of every further centre;
+ * n_local_trials = 2 + int(ln k) in sklearn, 1 .. 8 here.
+ *   seeding (sklearn _kmeans_plusplus): per step an inclusive float64 cumulative sum of the closest squared distances
+ *     (Hillis-Steele inside blocks of 256, block offsets added in ascending order), searchsorted-left of u * potential
+ *     clipped to ntotal - 1, distances of all rows to the candidates, one potential per candidate, the first smallest wins;
+ *   Lloyd (sklearn _kmeans_single_lloyd): assignment by argmin over |x|^2 + |c|^2 - 2 x.c (f64 MFMA, ties to the lower
+ *     centre), centres as per-centre sums over rows in ascending order (chunks of 512 rows, chunks in ascending order)
+ *     divided by the counts; stops when no label changed, else when sum |c_new - c_old|^2 <= tol, and then assigns once more
+ *     against the final centres; at most max_iter iterations (sklearn: 300); tol = tol_scale (sklearn: 1e-4) times the mean
+ *     per-dimension variance of the rows, taken on the device in two passes;
+ *   best of n_init: a later init replaces the best only if its inertia sum |x - c_label|^2 is strictly lower and it is not
+ *     the same partition under a renaming of the labels.
+ * All float64 in one fixed order, no floating-point atomics: two calls are bit-equal.  2 <= k <= 64
+ * (ANR_EINVAL beyond, and for k > ntotal).  A cluster that loses all its rows ends the call with ANR_EEMPTY: sklearn
+ * relocates such a centre through an argpartition whose order is not defined; nothing is written then but stats.
+ * Outputs (host; all but labels may be NULL): labels int32 [ntotal]; centres float64 [k][dim]; inertia; n_iter (Lloyd
+ * iterations of the winning init); best_init; stats (8 words): [0] Lloyd iterations of all inits, [1] assignment passes,
+ * [2] seeding steps, [3] bytes of scratch held on the handle, [4] MFMA steps per tile, [5] the init that emptied a cluster
+ * (-1: none), [6] inits that ended because no label changed, [7] the bits of the float64 tol. */
+#define ANR_EEMPTY (-6)  /* anr_index_kmeans: a cluster lost all its rows */
+int anr_index_kmeans(anr_index *h, int32_t k, int32_t n_init, int32_t n_local_trials, const int64_t *first_rows,
+                     const double *uniforms, int32_t max_iter, double tol_scale, int32_t *labels, double *centres,
+                     double *inertia, int32_t *n_iter, int32_t *best_init, int64_t *stats);
+
 /* tuning / introspection */
 #define ANR_OPT_FORCE_EXACT 1     /* 1: skip the f16 scan, run the dense exact path for every query  */
 #define ANR_OPT_OVERFETCH 2       /* candidates kept per query before the exact re-score (0 = auto)  */
