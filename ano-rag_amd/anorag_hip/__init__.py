@@ -9,3 +9,5 @@ from .topic_clustering import analyze_clusters, cluster_cohesion, silhouette_sam
 from .diversity import diversify  # noqa: F401
 from . import graph_quality  # noqa: F401
 from .graph_quality import compute_metrics  # noqa: F401
+from . import note_relations  # noqa: F401
+from .note_relations import SetJoin, entity_coexistence_relations, topic_relations  # noqa: F401

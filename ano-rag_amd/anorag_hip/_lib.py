@@ -37,6 +37,7 @@ ANR_ENOCONV = -5
 ANR_EEMPTY = -6
 NOTEGRAPH_OPT_MAX_SLOTS = 1
 NOTEGRAPH_OPT_BFS_WORDS = 2
+SETJOIN_OPT_TABLE_SLOTS = 1
 
 
 class AnoragError(RuntimeError):
@@ -270,6 +271,13 @@ SIGNATURES = {
     "anr_notegraph_components": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
     "anr_notegraph_hop_histogram": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                               C.POINTER(C.c_int64), C.c_void_p]),
+    "anr_setjoin_create": (C.c_int, [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    "anr_setjoin_destroy": (C.c_int, [C.c_void_p]),
+    "anr_setjoin_cooccur": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p]),
+    "anr_setjoin_cooccur_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]),
+    "anr_setjoin_pair_counts": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "anr_setjoin_set_option": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64]),
 }
 
 _lib = None

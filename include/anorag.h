@@ -751,6 +751,44 @@ int anr_notegraph_components(anr_notegraph *h, int32_t *labels_host /*[n]*/, int
 int anr_notegraph_hop_histogram(anr_notegraph *h, int64_t n_sources, const int64_t *sources, int64_t cap,
                                 int64_t *counts_host, int64_t *n_levels, int64_t *stats8);
 
+/* ------------------------------------------------------------------------------------------------
+ * Set-overlap join (opt-in): the two integer O(N^2) passes of RelationExtractor._extract_basic_relations
+ * (graph/relation_extractor.py:104-147).  A handle holds one family of sets on one device: the rows are notes, the items
+ * integer ids of entities or keywords, kept as a CSR and as its transpose (the postings).  No floating point: every output
+ * is an integer and the reference's last division stays with the caller.  Layout, the LDS table, the overflow rule and the
+ * cost per row: DESIGN.md §5k and the top of csrc/setjoin.hip.  Calls on one handle are serialised.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct anr_setjoin anr_setjoin;
+/* note_to_entities / entity_to_notes of relation_extractor.py:423-432: row r holds items[indptr[r] .. indptr[r+1]), STRICTLY
+ * ASCENDING ids in [0, n_items).  ANR_EINVAL, before any device work, for a row that descends or repeats an id, an id out of
+ * range, indptr not ascending from 0, a row of more than 2^20 items, n_rows or n_items or indptr[n_rows] >= 2^31 - 1.  The
+ * postings (item -> ascending rows) are built on the device by one stable radix sort of item << 32 | row.  Empty rows and
+ * n_rows == 0 are legal. */
+int anr_setjoin_create(int64_t n_rows, int64_t n_items, const int64_t *indptr, const int32_t *items, int32_t device,
+                       anr_setjoin **out);
+int anr_setjoin_destroy(anr_setjoin *h);
+/* The pair search of extract_entity_coexistence_relations (relation_extractor.py:434-463): every pair i < j with
+ * |S_i & S_j| >= min_common (min_common >= 1, ANR_EINVAL otherwise).  The result stays on the handle until the next call;
+ * *n_pairs and *n_common (may be NULL) = the pairs and the shared items over all of them.  A result that does not fit in
+ * the device's free memory is ANR_EHIP with the sizes in the message, never a truncation.
+ * stats8 (may be NULL), int64 [8]: 0 rows that had candidates to look at, 1 candidate insertions into the table, 2 pairs kept,
+ * 3 shared ids written, 4 rows_overflowed (rows that needed more than one pass of the table), 5 table slots, 6 passes summed
+ * over the rows, 7 scratch bytes besides the result. */
+int anr_setjoin_cooccur(anr_setjoin *h, int32_t min_common, int64_t *n_pairs, int64_t *n_common, int64_t *stats8);
+/* the pairs sorted by (i, j): I, J, inter = |S_i & S_j|, uni = |S_i| + |S_j| - inter (what :476 divides by), and the shared
+ * ids of pair p ascending in common_items[common_ptr[p] .. common_ptr[p+1]) (:460).  ANR_ESTATE before a cooccur call. */
+int anr_setjoin_cooccur_fetch(anr_setjoin *h, int32_t *I /*[n_pairs]*/, int32_t *J, int32_t *inter, int32_t *uni,
+                              int64_t *common_ptr /*[n_pairs+1]*/, int32_t *common_items /*[n_common]*/);
+/* the two set sizes of _calculate_note_topic_similarity (relation_extractor.py:752-753, :761-762) for n explicit row pairs:
+ * inter[p] = |S_I[p] & S_J[p]|, uni[p] = |S_I[p] | S_J[p]|.  i == j, empty rows and n == 0 are legal; a row outside
+ * [0, n_rows) is ANR_EINVAL.  Does not touch the cooccur result. */
+int anr_setjoin_pair_counts(anr_setjoin *h, int64_t n, const int32_t *I, const int32_t *J, int32_t *inter, int32_t *uni);
+/* option 1 = ANR_SETJOIN_OPT_TABLE_SLOTS — the slots of the LDS table a workgroup of anr_setjoin_cooccur accumulates a row's
+ * candidates in: a power of two in [64, 4096] (0 = the default, 4096).  Tests force 64 to walk the overflow passes on small
+ * inputs.  Results never depend on it. */
+#define ANR_SETJOIN_OPT_TABLE_SLOTS 1
+int anr_setjoin_set_option(anr_setjoin *h, int32_t option, int64_t value);
+
 #ifdef __cplusplus
 }
 #endif
