@@ -612,44 +612,27 @@ using namespace anr;
 struct anr_bm25 {
   int device = 0;
   int64_t n_docs = 0, n_terms = 0, nnz = 0;
-  int64_t *indptr = nullptr;
-  int32_t *docs = nullptr;
-  double *weights = nullptr;
+  DevBuf<int64_t> indptr;
+  DevBuf<int32_t> docs;
+  DevBuf<double> weights;
   hipStream_t stream = nullptr;
   std::mutex mu;
   // per-handle work space, grown on demand and kept (three hipMalloc / hipFree pairs per call were most of a
   // single-query bm25_scores): query offsets + terms, and the score rows of the host-output entry points
-  char *q_buf = nullptr;
-  int64_t q_cap = 0;
-  double *score_buf = nullptr;
-  int64_t score_cap = 0;
-  unsigned long long *max_ord = nullptr;  // [max_ord_cap] row maxima of the range-split scoring (ordered images)
-  int64_t max_ord_cap = 0;
+  DevBuf<char> q_buf;
+  DevBuf<double> score_buf;
+  DevBuf<unsigned long long> max_ord;  // row maxima of the range-split scoring (ordered images)
   int n_cu = 256;
   // the sliced sparse rows (cap > kSpMaxCap): host copy of the posting-list offsets (the slices are sized from the summed
   // list lengths), the slices' staging runs and the slice table
   std::vector<int64_t> h_indptr;
-  unsigned *st_id = nullptr;
-  double *st_val = nullptr;
-  int *st_cnt = nullptr;
-  int64_t st_cap = 0;      // slices the staging buffers hold
-  int *slice_base = nullptr;
-  int64_t slice_base_cap = 0;
+  DevBuf<unsigned> st_id;  // [slices][kSrSlice]
+  DevBuf<double> st_val;   // [slices][kSrSlice]
+  DevBuf<int> st_cnt;      // [slices]: its capacity is the slices the staging buffers hold
+  DevBuf<int> slice_base;
 };
 
 namespace {
-template <typename T>
-int b_alloc(T **p, int64_t n) {
-  *p = nullptr;
-  ANR_HIP(hipMalloc(reinterpret_cast<void **>(p), (size_t)(n > 0 ? n : 1) * sizeof(T)));
-  return ANR_OK;
-}
-template <typename T>
-void b_free(T *&p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
-
 int validate_queries(const anr_bm25 *h, int64_t nq, const int64_t *q_indptr, const int32_t *q_terms) {
   if (!h || nq < 0 || !q_indptr) return fail(ANR_EINVAL, "bad argument");
   if (q_indptr[0] != 0) return fail(ANR_EINVAL, "q_indptr[0] must be 0");
@@ -670,14 +653,9 @@ int upload_queries(anr_bm25 *h, int64_t nq, const int64_t *q_indptr, const int32
   rel.resize(nq + 1);
   for (int64_t i = 0; i <= nq; ++i) rel[i] = q_indptr[i] - q_indptr[0];
   const int64_t q_bytes = (nq + 1) * 8 + (nt > 0 ? nt : 1) * 4;
-  if (q_bytes > h->q_cap) {
-    b_free(h->q_buf);
-    h->q_cap = 0;
-    ANR_TRY(b_alloc(&h->q_buf, q_bytes + q_bytes / 2));
-    h->q_cap = q_bytes + q_bytes / 2;
-  }
-  int64_t *dq = reinterpret_cast<int64_t *>(h->q_buf);
-  int32_t *dt = reinterpret_cast<int32_t *>(h->q_buf + (nq + 1) * 8);
+  ANR_TRY(h->q_buf.alloc(q_bytes, "bm25", q_bytes + q_bytes / 2));
+  int64_t *dq = reinterpret_cast<int64_t *>(h->q_buf.p);
+  int32_t *dt = reinterpret_cast<int32_t *>(h->q_buf.p + (nq + 1) * 8);
   hipError_t e = hipMemcpyAsync(dq, rel.data(), (size_t)(nq + 1) * 8, hipMemcpyHostToDevice, h->stream);
   if (e == hipSuccess && nt > 0)
     e = hipMemcpyAsync(dt, q_terms + q_indptr[0], (size_t)nt * 4, hipMemcpyHostToDevice, h->stream);
@@ -695,18 +673,13 @@ int score_chunk(anr_bm25 *h, int64_t nq, const int64_t *q_indptr, const int32_t 
   if (into) {
     *d_scores = into;
   } else {
-    if (nq * h->n_docs > h->score_cap) {
-      b_free(h->score_buf);
-      h->score_cap = 0;
-      ANR_TRY(b_alloc(&h->score_buf, nq * h->n_docs));
-      h->score_cap = nq * h->n_docs;
-    }
-    *d_scores = h->score_buf;
+    ANR_TRY(h->score_buf.alloc(nq * h->n_docs, "bm25"));
+    *d_scores = h->score_buf.p;
   }
   ANR_TRY(upload_queries(h, nq, q_indptr, q_terms, rel, &dq, &dt));
   hipError_t e = hipMemsetAsync(*d_scores, 0, (size_t)nq * h->n_docs * 8, h->stream);
   if (e == hipSuccess) {
-    Bm25Params p{h->indptr, h->docs, h->weights, h->n_docs, dq, dt, *d_scores, normalize, max_into};
+    Bm25Params p{h->indptr.p, h->docs.p, h->weights.p, h->n_docs, dq, dt, *d_scores, normalize, max_into};
     // document ranges per query: enough workgroups to fill the chip four times over (one query: 32 slices), none for a
     // corpus too small to be worth slicing
     int R = (int)std::min<int64_t>(32, std::max<int64_t>(1, ceil_div((int64_t)4 * h->n_cu, nq)));
@@ -715,14 +688,9 @@ int score_chunk(anr_bm25 *h, int64_t nq, const int64_t *q_indptr, const int32_t 
       hipLaunchKernelGGL(k_bm25, dim3((unsigned)nq), dim3(1024), 0, h->stream, p);
       e = hipGetLastError();
     } else {
-      if (h->max_ord_cap < nq) {
-        b_free(h->max_ord);
-        h->max_ord_cap = 0;
-        ANR_TRY(b_alloc(&h->max_ord, nq));
-        h->max_ord_cap = nq;
-      }
-      e = hipMemsetAsync(h->max_ord, 0, (size_t)nq * 8, h->stream);
-      Bm25RangeParams rp{p, R, h->max_ord};
+      ANR_TRY(h->max_ord.alloc(nq, "bm25"));
+      e = hipMemsetAsync(h->max_ord.p, 0, (size_t)nq * 8, h->stream);
+      Bm25RangeParams rp{p, R, h->max_ord.p};
       if (e == hipSuccess) {
         hipLaunchKernelGGL(k_bm25_range_add, dim3((unsigned)nq, (unsigned)R), dim3(1024), 0, h->stream, rp);
         if (normalize || max_into)
@@ -762,37 +730,23 @@ int sparse_sliced(anr_bm25 *h, int64_t nq, const int64_t *q_indptr, const int32_
     const int64_t m = q1 - q0;
     base.assign((size_t)m + 1, 0);
     for (int64_t i = 0; i < m; ++i) base[i + 1] = base[i] + n_sl[q0 + i];
-    if (total > h->st_cap) {
-      b_free(h->st_id);
-      b_free(h->st_val);
-      b_free(h->st_cnt);
-      h->st_cap = 0;
+    if (total > h->st_cnt.cap) {  // all three go before the first comes back: the peak is one set, not two
+      h->st_id.release(), h->st_val.release(), h->st_cnt.release();
       const int64_t want = total + total / 4;
-      ANR_TRY(b_alloc(&h->st_id, want * kSrSlice));
-      ANR_TRY(b_alloc(&h->st_val, want * kSrSlice));
-      ANR_TRY(b_alloc(&h->st_cnt, want));
-      h->st_cap = want;
+      ANR_TRY(h->st_id.alloc(want * kSrSlice, "bm25"));
+      ANR_TRY(h->st_val.alloc(want * kSrSlice, "bm25"));
+      ANR_TRY(h->st_cnt.alloc(want, "bm25"));
     }
-    if (m + 1 > h->slice_base_cap) {
-      b_free(h->slice_base);
-      h->slice_base_cap = 0;
-      ANR_TRY(b_alloc(&h->slice_base, 2 * (m + 1)));
-      h->slice_base_cap = 2 * (m + 1);
-    }
-    if (h->max_ord_cap < m) {
-      b_free(h->max_ord);
-      h->max_ord_cap = 0;
-      ANR_TRY(b_alloc(&h->max_ord, m));
-      h->max_ord_cap = m;
-    }
+    ANR_TRY(h->slice_base.alloc(m + 1, "bm25", 2 * (m + 1)));
+    ANR_TRY(h->max_ord.alloc(m, "bm25"));
     int64_t *dq = nullptr;
     int32_t *dt = nullptr;
     ANR_TRY(upload_queries(h, m, q_indptr + q0, q_terms, rel, &dq, &dt));
-    hipError_t e = hipMemcpyAsync(h->slice_base, base.data(), (size_t)(m + 1) * 4, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(h->max_ord, 0, (size_t)m * 8, h->stream);
+    hipError_t e = hipMemcpyAsync(h->slice_base.p, base.data(), (size_t)(m + 1) * 4, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(h->max_ord.p, 0, (size_t)m * 8, h->stream);
     if (e == hipSuccess) {
-      Bm25SliceParams p{h->indptr, h->docs, h->weights, h->n_docs, dq, dt, h->slice_base, (int)m, normalize, cap,
-                        h->st_id, h->st_val, h->st_cnt, h->max_ord, ids_dev + q0 * cap, scores_dev + q0 * cap,
+      Bm25SliceParams p{h->indptr.p, h->docs.p, h->weights.p, h->n_docs, dq, dt, h->slice_base.p, (int)m, normalize, cap,
+                        h->st_id.p, h->st_val.p, h->st_cnt.p, h->max_ord.p, ids_dev + q0 * cap, scores_dev + q0 * cap,
                         count_dev + q0, max_dev ? max_dev + q0 : nullptr};
       if (total > 0) hipLaunchKernelGGL(k_bm25_slice, dim3((unsigned)total), dim3(1024), (size_t)kSrLds, h->stream, p);
       hipLaunchKernelGGL(k_bm25_slice_pack, dim3((unsigned)m), dim3(1024), 0, h->stream, p);
@@ -839,13 +793,13 @@ int anr_bm25_create(int32_t device, int64_t n_docs, int64_t n_terms, const int64
   int rc = ANR_OK;
   h->n_cu = device_cu_count(device);
   if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) rc = fail(ANR_EHIP, "hipStreamCreate failed");
-  if (rc == ANR_OK) rc = b_alloc(&h->indptr, n_terms + 1);
-  if (rc == ANR_OK) rc = b_alloc(&h->docs, nnz);
-  if (rc == ANR_OK) rc = b_alloc(&h->weights, nnz);
+  if (rc == ANR_OK) rc = h->indptr.alloc(n_terms + 1, "bm25");
+  if (rc == ANR_OK) rc = h->docs.alloc(nnz, "bm25");
+  if (rc == ANR_OK) rc = h->weights.alloc(nnz, "bm25");
   if (rc == ANR_OK) {
-    hipError_t e = hipMemcpy(h->indptr, indptr, (size_t)(n_terms + 1) * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess && nnz > 0) e = hipMemcpy(h->docs, doc_ids, (size_t)nnz * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess && nnz > 0) e = hipMemcpy(h->weights, weights, (size_t)nnz * 8, hipMemcpyHostToDevice);
+    hipError_t e = hipMemcpy(h->indptr.p, indptr, (size_t)(n_terms + 1) * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess && nnz > 0) e = hipMemcpy(h->docs.p, doc_ids, (size_t)nnz * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && nnz > 0) e = hipMemcpy(h->weights.p, weights, (size_t)nnz * 8, hipMemcpyHostToDevice);
     if (e != hipSuccess) rc = fail(ANR_EHIP, "upload failed: %s", hipGetErrorString(e));
   }
   if (rc != ANR_OK) {
@@ -860,18 +814,8 @@ int anr_bm25_destroy(anr_bm25 *h) {
   if (!h) return ANR_OK;
   DeviceGuard g(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  b_free(h->indptr);
-  b_free(h->docs);
-  b_free(h->weights);
-  b_free(h->q_buf);
-  b_free(h->max_ord);
-  b_free(h->st_id);
-  b_free(h->st_val);
-  b_free(h->st_cnt);
-  b_free(h->slice_base);
-  b_free(h->score_buf);
   if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
+  delete h;  // frees the handle's buffers, still under the guard
   return ANR_OK;
 }
 
@@ -923,7 +867,8 @@ int anr_bm25_sparse_dev(anr_bm25 *h, int64_t nq, const int64_t *q_indptr, const 
   ANR_TRY(upload_queries(h, nq, q_indptr, q_terms, rel, &dq, &dt));
   const int lds = kSpTable * 12;
   ANR_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(k_bm25_sparse), lds));
-  Bm25SparseParams p{h->indptr, h->docs, h->weights, h->n_docs, dq, dt, normalize, cap, ids_dev, scores_dev, count_dev, max_dev};
+  Bm25SparseParams p{h->indptr.p, h->docs.p, h->weights.p, h->n_docs, dq,      dt,
+                     normalize,   cap,       ids_dev,      scores_dev, count_dev, max_dev};
   hipLaunchKernelGGL(k_bm25_sparse, dim3((unsigned)nq), dim3(1024), (size_t)lds, h->stream, p);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess && out_count_host)
@@ -971,27 +916,22 @@ int anr_bm25_nonzero(anr_bm25 *h, int64_t nq, const int64_t *q_indptr, const int
   const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(nq, (int64_t)(1ll << 31) / (h->n_docs * 8)));
   for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
     const int64_t m = std::min(chunk, nq - q0);
-    double *d = nullptr, *dsc = nullptr;
-    int32_t *ddoc = nullptr;
-    int *dcnt = nullptr;
-    int rc = score_chunk(h, m, q_indptr + q0, q_terms, normalize, &d);
-    if (rc == ANR_OK) rc = b_alloc(&ddoc, m * cap);
-    if (rc == ANR_OK) rc = b_alloc(&dsc, m * cap);
-    if (rc == ANR_OK) rc = b_alloc(&dcnt, m);
-    if (rc == ANR_OK) {
-      NzParams np{d, h->n_docs, cap, ddoc, dsc, dcnt};
-      hipLaunchKernelGGL(k_bm25_nonzero, dim3((unsigned)m), dim3(1024), 0, h->stream, np);
-      hipError_t e = hipGetLastError();
-      if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-      if (e == hipSuccess) e = hipMemcpy(out_docs + q0 * cap, ddoc, (size_t)m * cap * 4, hipMemcpyDeviceToHost);
-      if (e == hipSuccess) e = hipMemcpy(out_scores + q0 * cap, dsc, (size_t)m * cap * 8, hipMemcpyDeviceToHost);
-      if (e == hipSuccess) e = hipMemcpy(out_count + q0, dcnt, (size_t)m * 4, hipMemcpyDeviceToHost);
-      if (e != hipSuccess) rc = fail(ANR_EHIP, "bm25 nonzero failed: %s", hipGetErrorString(e));
-    }
-    b_free(ddoc);  // (d points into the handle's score buffer)
-    b_free(dsc);
-    b_free(dcnt);
-    if (rc != ANR_OK) return rc;
+    double *d = nullptr;  // points into the handle's score buffer
+    DevBuf<double> dsc;   // the three of this chunk
+    DevBuf<int32_t> ddoc;
+    DevBuf<int> dcnt;
+    ANR_TRY(score_chunk(h, m, q_indptr + q0, q_terms, normalize, &d));
+    ANR_TRY(ddoc.alloc(m * cap, "bm25"));
+    ANR_TRY(dsc.alloc(m * cap, "bm25"));
+    ANR_TRY(dcnt.alloc(m, "bm25"));
+    NzParams np{d, h->n_docs, cap, ddoc.p, dsc.p, dcnt.p};
+    hipLaunchKernelGGL(k_bm25_nonzero, dim3((unsigned)m), dim3(1024), 0, h->stream, np);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess) e = hipMemcpy(out_docs + q0 * cap, ddoc.p, (size_t)m * cap * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_scores + q0 * cap, dsc.p, (size_t)m * cap * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_count + q0, dcnt.p, (size_t)m * 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(ANR_EHIP, "bm25 nonzero failed: %s", hipGetErrorString(e));
   }
   return ANR_OK;
 }

@@ -15,27 +15,6 @@ using namespace anr;
 
 namespace {
 
-// device buffers of one call
-struct DevBuf {
-  void *p = nullptr;
-  ~DevBuf() { release(); }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-  }
-  int alloc(size_t bytes) {
-    release();
-    if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) {
-      p = nullptr;
-      (void)hipGetLastError();
-      return fail(ANR_EHIP, "dbscan: could not allocate %zu bytes of device memory", bytes);
-    }
-    return ANR_OK;
-  }
-  template <typename T>
-  T *as() const { return static_cast<T *>(p); }
-};
-
 template <int PASS>
 int launch_walk(const DbscanWalk &w, int n_cu, hipStream_t st) {
   constexpr int slots_bytes = 2 * 4 * 16 * 1024;
@@ -93,14 +72,17 @@ extern "C" int anr_index_dbscan(anr_index *h, double eps, int32_t min_samples, i
   if (pg.grid() > 0x7fffffffLL) return fail(ANR_EINVAL, "too many rows for one dbscan launch");
 
   hipStream_t st = v.stream;
-  DevBuf count, parent, border, rank, labels, blk, counters, cand, inpairs;
-  ANR_TRY(count.alloc((size_t)n * 4));
-  ANR_TRY(parent.alloc((size_t)n * 4));
-  ANR_TRY(border.alloc((size_t)n * 4));
-  ANR_TRY(rank.alloc((size_t)n * 4));
-  ANR_TRY(labels.alloc((size_t)n * 4));
-  ANR_TRY(blk.alloc((size_t)nblk * 4));
-  ANR_TRY(counters.alloc(kDbCounters * 8));
+  DevBuf<unsigned> count, parent, border, rank, blk;  // buffers of this call
+  DevBuf<int> labels;
+  DevBuf<unsigned long long> counters;
+  DevBuf<uint2> cand, inpairs;
+  ANR_TRY(count.alloc(n, "dbscan"));
+  ANR_TRY(parent.alloc(n, "dbscan"));
+  ANR_TRY(border.alloc(n, "dbscan"));
+  ANR_TRY(rank.alloc(n, "dbscan"));
+  ANR_TRY(labels.alloc(n, "dbscan"));
+  ANR_TRY(blk.alloc(nblk, "dbscan"));
+  ANR_TRY(counters.alloc(kDbCounters, "dbscan"));
   unsigned long long hc[kDbCounters] = {};
 
   DbscanWalk w{};
@@ -113,18 +95,18 @@ extern "C" int anr_index_dbscan(anr_index *h, double eps, int32_t min_samples, i
   w.n_slots = pg.grid();
   w.thr_hi = f32_above(thr + band);
   w.thr_lo = f32_below(thr - band);
-  w.count = count.as<unsigned>();
-  w.blk = blk.as<unsigned>();
-  w.parent = parent.as<unsigned>();
-  w.border = border.as<unsigned>();
-  w.counters = counters.as<unsigned long long>();
+  w.count = count.p;
+  w.blk = blk.p;
+  w.parent = parent.p;
+  w.border = border.p;
+  w.counters = counters.p;
 
   // degree pass; the undecided pairs go to a list that is grown to what the pass reports if it was too short
   int64_t walks = 0, retries = 0;
   int64_t cap = std::max<int64_t>(4 * n, 1 << 16);
   for (;;) {
-    ANR_TRY(cand.alloc((size_t)cap * sizeof(uint2)));
-    w.cand = cand.as<uint2>();
+    ANR_TRY(cand.alloc(cap, "dbscan"));
+    w.cand = cand.p;
     w.cap = (unsigned long long)cap;
     ANR_HIP(hipMemsetAsync(count.p, 0, (size_t)n * 4, st));
     ANR_HIP(hipMemsetAsync(counters.p, 0, kDbCounters * 8, st));
@@ -141,24 +123,24 @@ extern "C" int anr_index_dbscan(anr_index *h, double eps, int32_t min_samples, i
   DbscanRows r{};
   r.n = n;
   r.min_samples = min_samples;
-  r.count = count.as<unsigned>();
-  r.blk = blk.as<unsigned>();
-  r.parent = parent.as<unsigned>();
-  r.border = border.as<unsigned>();
-  r.rank = rank.as<unsigned>();
-  r.labels = labels.as<int>();
-  r.counters = counters.as<unsigned long long>();
+  r.count = count.p;
+  r.blk = blk.p;
+  r.parent = parent.p;
+  r.border = border.p;
+  r.rank = rank.p;
+  r.labels = labels.p;
+  r.counters = counters.p;
   const unsigned list_grid = (unsigned)std::min<int64_t>(std::max<int64_t>(ceil_div((int64_t)n_unc, 256), 1), (int64_t)v.n_cu * 16);
   if (n_unc > 0) {
-    ANR_TRY(inpairs.alloc((size_t)n_unc * sizeof(uint2)));
-    DbscanResolve rp{v.x32, v.dim, l2 ? 1 : 0, cand.as<uint2>(), n_unc, eps, count.as<unsigned>(), inpairs.as<uint2>(),
-                     counters.as<unsigned long long>()};
+    ANR_TRY(inpairs.alloc((int64_t)n_unc, "dbscan"));
+    DbscanResolve rp{v.x32, v.dim, l2 ? 1 : 0, cand.p, n_unc, eps, count.p, inpairs.p,
+                     counters.p};
     hipLaunchKernelGGL(k_dbscan_resolve, dim3(list_grid), dim3(256), 0, st, rp);
     ANR_HIP(hipGetLastError());
     ANR_HIP(hipMemcpyAsync(hc, counters.p, sizeof hc, hipMemcpyDeviceToHost, st));
     ANR_HIP(hipStreamSynchronize(st));
     cand.release();
-    r.in_pairs = inpairs.as<uint2>();
+    r.in_pairs = inpairs.p;
     r.n_pairs = hc[kDbResolvedIn];
   }
 
@@ -174,12 +156,12 @@ extern "C" int anr_index_dbscan(anr_index *h, double eps, int32_t min_samples, i
   // pointer jumping to the fixpoint: a round halves every path, so 64 rounds are more than any forest needs
   int64_t rounds = 0;
   for (; rounds < 64;) {
-    ANR_HIP(hipMemsetAsync(counters.as<unsigned long long>() + kDbChanged, 0, 8, st));
+    ANR_HIP(hipMemsetAsync(counters.p + kDbChanged, 0, 8, st));
     hipLaunchKernelGGL(k_dbscan_jump, dim3((unsigned)nblk), dim3(256), 0, st, r);
     ANR_HIP(hipGetLastError());
     ++rounds;
     unsigned long long changed = 0;
-    ANR_HIP(hipMemcpyAsync(&changed, counters.as<unsigned long long>() + kDbChanged, 8, hipMemcpyDeviceToHost, st));
+    ANR_HIP(hipMemcpyAsync(&changed, counters.p + kDbChanged, 8, hipMemcpyDeviceToHost, st));
     ANR_HIP(hipStreamSynchronize(st));
     if (!changed) break;
     if (rounds == 64) return fail(ANR_EHIP, "dbscan: pointer jumping did not converge");

@@ -2,9 +2,9 @@
 // TopicClustering._analyze_clusters (doc/clustering.py:171-215) on the stored rows of an L2 index — sklearn's Euclidean
 // silhouette of every row (the noise label -1 counted as a cluster) and, per cluster, the mean and the population
 // standard deviation of scipy's cosine distance over its pairs.  Everything comes from one float64 Gram G = X X^T formed
-// with v_mfma_f64_16x16x4_f64 in one fixed k-order, as in diversity.hip; the rows are first sorted by label with the
-// stable radix sort, so that a label is a run of consecutive positions.  DESIGN.md §5h has the tile walk, the lane-to-row
-// reduction, the determinism rule and the error bounds.  Compiled without multiply-add contraction (Makefile, EXACT).
+// with the tile diversity.hip uses (gram_f64.hpp: the lane map and the determinism rule); the rows are first sorted by
+// label with the stable radix sort, so that a label is a run of consecutive positions.  DESIGN.md §5h has the tile walk,
+// the lane-to-row reduction and the error bounds.  Compiled without multiply-add contraction (Makefile, EXACT).
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -12,68 +12,24 @@
 #include <mutex>
 #include <vector>
 
-#include "cluster_quality.hpp"
 #include "common.hpp"
+#include "gram_f64.hpp"
+#include "graph.hpp"
 
 using namespace anr;
-
-// scratch kept on the index handle between calls, grown on demand
-struct anr_cluster_quality {
-  void *arena = nullptr;  // every array of one call
-  size_t arena_cap = 0;
-};
-
-namespace anr {
-void cluster_quality_free(anr_cluster_quality *q) {
-  if (!q) return;
-  if (q->arena) (void)hipFree(q->arena);
-  delete q;
-}
-}  // namespace anr
 
 namespace {
 
 constexpr int kCqTile = 64;  // a workgroup's tile: 4 waves of 16 rows x 64 columns (four 16 x 16 MFMA blocks each)
-constexpr int kCqKC = 64;    // k-chunk staged through LDS
 constexpr int kCqLd = 68;    // row length in LDS: the 64 lanes of an operand read, (lane & 15) * 68 + (lane >> 4), hit 64 banks
 constexpr int kCqNT = 256;
 
-typedef double double4_t __attribute__((ext_vector_type(4)));
-
-// Raw products of one 64 x 64 tile of G = X X^T with v_mfma_f64_16x16x4_f64: the rows named by ra (tile rows) and rb (tile
-// columns), -1 = padding.  Operand lanes: A[i][k] and B[k][j] both sit in lane (i or j) + 16 k, one double each; result
-// register r of block b of wave w is row 16 w + (lane >> 4) + 4 r, column 16 b + (lane & 15).  Every tile, whatever its
-// position, runs the same ceil(dim / 64) * 16 steps over k in ascending order with padding rows and k beyond dim as exact
-// zeros: G_ij is one fixed sequence of additions of exact products of rows i and j — the same one on the diagonal, so
-// identical rows have G_ii = G_ij = G_jj bit for bit.  Ends with a barrier.
+// Raw products of one 64 x 64 tile of G = X X^T, the rows named by ra (tile rows) and rb (tile columns), -1 = padding: the
+// shared tile with 4 x 1 waves of four 16 x 16 blocks each.  Result register r of block b of wave w is row
+// 16 w + (lane >> 4) + 4 r, column 16 b + (lane & 15).  Ends with a barrier.
 __device__ __forceinline__ void cq_tile_gram(const float *__restrict__ x32, int dim, const int64_t *ra, const int64_t *rb,
                                              float (*As)[kCqLd], float (*Bs)[kCqLd], double4_t acc[4]) {
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-#pragma unroll
-  for (int b = 0; b < 4; ++b) acc[b] = double4_t{0.0, 0.0, 0.0, 0.0};
-  for (int k0 = 0; k0 < dim; k0 += kCqKC) {
-    for (int e = tid; e < kCqTile * kCqKC; e += kCqNT) {
-      const int r = e / kCqKC, k = e % kCqKC, kk = k0 + k;
-      float va = 0.f, vb = 0.f;
-      if (kk < dim) {
-        if (ra[r] >= 0) va = x32[ra[r] * dim + kk];
-        if (rb[r] >= 0) vb = x32[rb[r] * dim + kk];
-      }
-      As[r][k] = va;
-      Bs[r][k] = vb;
-    }
-    __syncthreads();
-#pragma unroll 4
-    for (int ks = 0; ks < kCqKC; ks += 4) {
-      const double a = (double)As[w * 16 + (lane & 15)][ks + (lane >> 4)];
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        const double bv = (double)Bs[b * 16 + (lane & 15)][ks + (lane >> 4)];
-        acc[b] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bv, acc[b], 0, 0, 0);
-      }
-    }
-    __syncthreads();
-  }
+  gram_f64_tile<4, 1, 4, kCqLd>(x32, dim, ra, rb, As, Bs, acc);
 }
 
 // positions are places in the label-sorted order; perm[position] is the stored row
@@ -311,26 +267,6 @@ __global__ __launch_bounds__(kCqNT) void k_cq_coh_reduce(const double *partial, 
 bool g_timing = false;
 float g_times[3] = {0.f, 0.f, 0.f};  // silhouette group, cohesion group, first copy in to last copy out
 
-struct Events {
-  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool on = false;
-  int init() {
-    on = true;
-    for (auto &x : e) ANR_HIP(hipEventCreate(&x));
-    return ANR_OK;
-  }
-  int mark(int i, hipStream_t st) {
-    if (on) ANR_HIP(hipEventRecord(e[i], st));
-    return ANR_OK;
-  }
-  ~Events() {
-    for (auto &x : e)
-      if (x) (void)hipEventDestroy(x);
-  }
-};
-
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 
 extern "C" int anr_cluster_quality_timing(int32_t enable, float *ms3) {
@@ -399,37 +335,21 @@ extern "C" int anr_index_cluster_quality(anr_index *h, const int32_t *labels_hos
   if (n_tiles > 0x7fffffffLL) return fail(ANR_EINVAL, "cluster quality: too many cluster tiles for one launch");
 
   // arena: inputs (one copy in), work arrays, outputs (one copy back)
-  size_t at = 0;
-  auto take = [&](size_t bytes) {
-    const size_t r = at;
-    at = al256(at + bytes);
-    return r;
-  };
-  const size_t o_labels = take((size_t)n * 4), o_segpos = take((size_t)n * 4), o_segstart = take((size_t)(nl + 1) * 4);
-  const size_t o_cstart = take((size_t)nc * 4), o_csize = take((size_t)nc * 4), o_toff = take((size_t)(nc + 1) * 8);
-  const size_t o_tiles = take(tiles.size() * 4), in_end = at;
-  const size_t o_kin = take((size_t)n * 8), o_kout = take((size_t)n * 8), o_iota = take((size_t)n * 4);
-  const size_t o_perm = take((size_t)n * 4), o_nrm2 = take((size_t)n * 8), o_partial = take((size_t)n_tiles * 8);
-  const size_t o_sort = take(radix_sort_temp_bytes(n));
-  const size_t o_out = at;
-  const size_t o_sil = take((size_t)n * 8), o_mean = take(8), o_cmean = take((size_t)nc * 8), o_csd = take((size_t)nc * 8);
-  const size_t out_end = at;
+  ArenaLayout<256> L;
+  const size_t o_labels = L.take((size_t)n * 4), o_segpos = L.take((size_t)n * 4), o_segstart = L.take((size_t)(nl + 1) * 4);
+  const size_t o_cstart = L.take((size_t)nc * 4), o_csize = L.take((size_t)nc * 4), o_toff = L.take((size_t)(nc + 1) * 8);
+  const size_t o_tiles = L.take(tiles.size() * 4), in_end = L.at;
+  const size_t o_kin = L.take((size_t)n * 8), o_kout = L.take((size_t)n * 8), o_iota = L.take((size_t)n * 4);
+  const size_t o_perm = L.take((size_t)n * 4), o_nrm2 = L.take((size_t)n * 8), o_partial = L.take((size_t)n_tiles * 8);
+  const size_t o_sort = L.take(radix_sort_temp_bytes(n));
+  const size_t o_out = L.at;
+  const size_t o_sil = L.take((size_t)n * 8), o_mean = L.take(8), o_cmean = L.take((size_t)nc * 8);
+  const size_t o_csd = L.take((size_t)nc * 8);
+  const size_t out_end = L.at;
 
-  anr_cluster_quality *&q = index_cluster_quality(h);
-  if (!q) q = new anr_cluster_quality();
-  if (out_end > q->arena_cap) {
-    if (q->arena) (void)hipFree(q->arena);
-    q->arena = nullptr;
-    q->arena_cap = 0;
-    const size_t want = out_end + out_end / 4;
-    if (hipMalloc(&q->arena, want) != hipSuccess) {
-      q->arena = nullptr;
-      (void)hipGetLastError();
-      return fail(ANR_EHIP, "cluster quality: could not allocate %zu bytes of device memory", want);
-    }
-    q->arena_cap = want;
-  }
-  unsigned char *A = static_cast<unsigned char *>(q->arena);
+  DevBuf<unsigned char> &arena = index_scratch(h).cq_arena;
+  ANR_TRY(arena.alloc((int64_t)out_end, "cluster quality", (int64_t)(out_end + out_end / 4)));
+  unsigned char *A = arena.p;
   hipStream_t st = cur.stream;
 
   std::vector<unsigned char> in(in_end, 0);
@@ -443,7 +363,7 @@ extern "C" int anr_index_cluster_quality(anr_index *h, const int32_t *labels_hos
   }
   memcpy(&in[o_toff], toff.data(), (size_t)(nc + 1) * 8);
 
-  Events ev;
+  Events<4> ev;
   if (g_timing) ANR_TRY(ev.init());
   ANR_TRY(ev.mark(0, st));
   ANR_HIP(hipMemcpyAsync(A, in.data(), in_end, hipMemcpyHostToDevice, st));
@@ -497,9 +417,9 @@ extern "C" int anr_index_cluster_quality(anr_index *h, const int32_t *labels_hos
   ANR_TRY(ev.mark(3, st));
   ANR_HIP(hipStreamSynchronize(st));
   if (ev.on) {
-    ANR_HIP(hipEventElapsedTime(&g_times[0], ev.e[0], ev.e[1]));
-    ANR_HIP(hipEventElapsedTime(&g_times[1], ev.e[1], ev.e[2]));
-    ANR_HIP(hipEventElapsedTime(&g_times[2], ev.e[0], ev.e[3]));
+    ANR_TRY(ev.elapsed(0, 1, &g_times[0]));
+    ANR_TRY(ev.elapsed(1, 2, &g_times[1]));
+    ANR_TRY(ev.elapsed(0, 3, &g_times[2]));
   }
   const unsigned char *O = out.data() - o_out;
   if (sil_samples) memcpy(sil_samples, O + o_sil, (size_t)n * 8);
@@ -524,8 +444,8 @@ extern "C" int anr_index_cluster_quality(anr_index *h, const int32_t *labels_hos
     stats[2] = want_sil ? (int64_t)strips * strips : 0;
     stats[3] = n_tiles;
     stats[4] = nc;
-    stats[5] = (int64_t)q->arena_cap;
-    stats[6] = (int64_t)ceil_div(cur.dim, kCqKC) * (kCqKC / 4);
+    stats[5] = arena.cap;
+    stats[6] = (int64_t)ceil_div(cur.dim, kGramKC) * (kGramKC / 4);
   }
   return ANR_OK;
 }

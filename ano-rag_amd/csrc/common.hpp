@@ -1,7 +1,11 @@
-// Shared host-side helpers for libanorag_hip.so (error reporting, HIP call checking).
+// Shared host-side helpers for libanorag_hip.so: error reporting and HIP call checking, the device guard, and the one
+// owner of device memory outside the scan and the encoder — DevBuf (a typed, move-only device buffer with a capacity),
+// ArenaLayout (offsets of the arrays carved from one buffer) and Events (HIP-event timing of a call).  The f64 MFMA Gram
+// tile that diversity.hip and cluster_quality.hip share is in gram_f64.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -46,6 +50,84 @@ struct DeviceGuard {
   }
 };
 
+// A typed device buffer with its capacity in elements.  Move-only; frees in its destructor, so a buffer of one call is
+// declared after the DeviceGuard it must not outlive, and a member of a handle is freed where the handle is deleted.
+template <typename T>
+struct DevBuf {
+  T *p = nullptr;
+  int64_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+  DevBuf &operator=(DevBuf &&o) noexcept {
+    if (this != &o) {
+      release();
+      p = o.p, cap = o.cap;
+      o.p = nullptr, o.cap = 0;
+    }
+    return *this;
+  }
+  ~DevBuf() { release(); }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+  // Room for n elements.  Nothing happens if it is there; otherwise the old block is freed (its contents are not kept)
+  // and max(n, want, 1) elements are allocated: `want` is the caller's growth rule, and a buffer of no elements still has
+  // a pointer.  `what` names the caller in the error text, `purpose` the buffer where the caller has several.
+  int alloc(int64_t n, const char *what, int64_t want = 0, const char *purpose = nullptr) {
+    if (p && n <= cap) return ANR_OK;
+    release();
+    const int64_t nc = std::max<int64_t>(std::max(n, want), 1);
+    const size_t bytes = (size_t)nc * sizeof(T);
+    if (hipMalloc(reinterpret_cast<void **>(&p), bytes) != hipSuccess) {
+      p = nullptr;
+      (void)hipGetLastError();  // the error is sticky
+      return fail(ANR_EHIP, "%s: could not allocate %zu bytes of device memory%s%s", what, bytes, purpose ? " for " : "",
+                  purpose ? purpose : "");
+    }
+    cap = nc;
+    return ANR_OK;
+  }
+};
+
+// byte offsets of the arrays of one call inside one device buffer, every one aligned to ALIGN bytes
+template <size_t ALIGN>
+struct ArenaLayout {
+  size_t at = 0;  // the end of what was taken so far
+  size_t take(size_t bytes) {
+    const size_t r = at;
+    at = (at + bytes + ALIGN - 1) & ~(ALIGN - 1);
+    return r;
+  }
+};
+
+// N HIP events for the developer timing of one call: nothing is created or recorded until init()
+template <int N>
+struct Events {
+  hipEvent_t e[N] = {};
+  bool on = false;
+  int init() {
+    on = true;
+    for (auto &x : e) ANR_HIP(hipEventCreate(&x));
+    return ANR_OK;
+  }
+  int mark(int i, hipStream_t st) {
+    if (on) ANR_HIP(hipEventRecord(e[i], st));
+    return ANR_OK;
+  }
+  int elapsed(int i, int j, float *ms) {
+    ANR_HIP(hipEventElapsedTime(ms, e[i], e[j]));
+    return ANR_OK;
+  }
+  ~Events() {
+    for (auto &x : e)
+      if (x) (void)hipEventDestroy(x);
+  }
+};
+
 int device_cu_count(int device);
 
 // device-wide stable radix sort of (key, u32 value) pairs (radix_sort.hip); temp: radix_sort_temp_bytes(n) bytes of device
@@ -58,10 +140,9 @@ int radix_sort_pairs_f32(void *temp, const float *k_in, float *k_out, const unsi
 
 // top-k beyond the select window (largek.hip): full device sort of one query's exact scores
 struct LargeKScratch {
-  unsigned *iota = nullptr, *rows = nullptr;
-  float *keys = nullptr;
-  void *temp = nullptr;
-  size_t temp_bytes = 0;
+  DevBuf<unsigned> iota, rows;
+  DevBuf<float> keys;
+  DevBuf<unsigned char> temp;
   int64_t n = 0;
 };
 int sort_topk(const float *scores_dev, int64_t n, int k, bool larger_is_better, int64_t id_offset, float *D_row,

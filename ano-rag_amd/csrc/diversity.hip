@@ -1,8 +1,9 @@
 // anr_index_diversify (include/anorag.h): semantic dedup and greedy diverse selection of fused candidates — the arithmetic
 // of the reference's DiversityScheduler.schedule_candidates (retrieval/diversity_scheduler.py:523) for a batch of queries.
 // k_div_gram + k_div_cosine build one C x C float64 cosine matrix per query from the index's stored rows (f64 MFMA);
-// k_div_select runs the decision procedure on it, one workgroup per query.  DESIGN.md §5g has the tile layout, the lane
-// map, the determinism rule and the error bound.  Compiled without multiply-add contraction (Makefile, EXACT).
+// k_div_select runs the decision procedure on it, one workgroup per query.  gram_f64.hpp has the lane map and the
+// determinism rule, DESIGN.md §5g the tile layout and the error bound.  Compiled without multiply-add contraction
+// (Makefile, EXACT).
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -10,36 +11,17 @@
 #include <vector>
 
 #include "common.hpp"
-#include "diversity.hpp"
+#include "gram_f64.hpp"
+#include "graph.hpp"
 
 using namespace anr;
-
-// scratch kept on the index handle between calls, grown on demand
-struct anr_diversity {
-  void *sim = nullptr;    // the per-query similarity matrices, float64
-  size_t sim_cap = 0;
-  void *arena = nullptr;  // every small input and output array of one call
-  size_t arena_cap = 0;
-};
-
-namespace anr {
-void diversity_free(anr_diversity *d) {
-  if (!d) return;
-  if (d->sim) (void)hipFree(d->sim);
-  if (d->arena) (void)hipFree(d->arena);
-  delete d;
-}
-}  // namespace anr
 
 namespace {
 
 constexpr int kDivMaxC = 1024;  // candidates per query
 constexpr int kDivTile = 32;    // a workgroup's tile of one query's matrix: 2 x 2 waves of 16 x 16
-constexpr int kDivKC = 64;      // k-chunk staged through LDS
-constexpr int kDivLd = kDivKC + 1;
+constexpr int kDivLd = kGramKC + 1;
 constexpr int kDivNT = 256;
-
-typedef double double4_t __attribute__((ext_vector_type(4)));
 
 struct DivGram {
   const float *x32;
@@ -52,10 +34,8 @@ struct DivGram {
   double *nrm;          // [total] sqrt(G_ii)
 };
 
-// Raw products G = A A^T of one 32 x 32 tile with v_mfma_f64_16x16x4_f64.  Operand lanes: A[i][k] and B[k][j] both sit in
-// lane (i or j) + 16 k, one double each; result register r of a lane is row (lane >> 4) + 4 r, column lane & 15.  Every
-// tile, whatever its position, runs the same ceil(dim / 64) * 16 steps over k in ascending order with rows and columns
-// beyond the list and k beyond dim as exact zeros: G_ij is one fixed sequence of additions of exact products of rows i, j.
+// Raw products G = A A^T of one 32 x 32 tile: the shared tile (gram_f64.hpp) with 2 x 2 waves of one 16 x 16 block each.
+// Result register r of a lane is row 16 wi + (lane >> 4) + 4 r, column 16 wj + (lane & 15).
 __global__ __launch_bounds__(kDivNT) void k_div_gram(DivGram p) {
   __shared__ float As[kDivTile][kDivLd], Bs[kDivTile][kDivLd];
   __shared__ int64_t ra[kDivTile], rb[kDivTile];
@@ -69,33 +49,14 @@ __global__ __launch_bounds__(kDivNT) void k_div_gram(DivGram p) {
     rb[tid] = ib < C ? p.rows[o + ib] : -1;
   }
   __syncthreads();
-  double4_t acc = {0.0, 0.0, 0.0, 0.0};
-  for (int k0 = 0; k0 < p.dim; k0 += kDivKC) {
-    for (int e = tid; e < kDivTile * kDivKC; e += kDivNT) {
-      const int r = e / kDivKC, k = e % kDivKC, kk = k0 + k;
-      float va = 0.f, vb = 0.f;
-      if (kk < p.dim) {
-        if (ra[r] >= 0) va = p.x32[ra[r] * p.dim + kk];
-        if (rb[r] >= 0) vb = p.x32[rb[r] * p.dim + kk];
-      }
-      As[r][k] = va;
-      Bs[r][k] = vb;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int ks = 0; ks < kDivKC; ks += 4) {
-      const double a = (double)As[wi * 16 + (lane & 15)][ks + (lane >> 4)];
-      const double b = (double)Bs[wj * 16 + (lane & 15)][ks + (lane >> 4)];
-      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
-    }
-    __syncthreads();
-  }
+  double4_t acc[1];
+  gram_f64_tile<2, 2, 1, kDivLd>(p.x32, p.dim, ra, rb, As, Bs, acc);
   double *G = p.G + p.soff[q];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int i = bi * kDivTile + wi * 16 + (lane >> 4) + 4 * r, j = bj * kDivTile + wj * 16 + (lane & 15);
     if (i < C && j < C) {
-      const double v = acc[r];
+      const double v = acc[0][r];
       G[(int64_t)i * C + j] = v;
       if (bi != bj) G[(int64_t)j * C + i] = v;  // tiles below the diagonal are not computed
       if (i == j) p.nrm[o + i] = sqrt(v);
@@ -355,39 +316,6 @@ __global__ __launch_bounds__(kDivNT) void k_div_select(DivSelect a) {
 bool g_timing = false;
 float g_times[3] = {0.f, 0.f, 0.f};  // similarity kernels, decision kernel, first copy in to last copy out
 
-struct Events {
-  hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  bool on = false;
-  int init() {
-    on = true;
-    for (auto &x : e) ANR_HIP(hipEventCreate(&x));
-    return ANR_OK;
-  }
-  int mark(int i, hipStream_t st) {
-    if (on) ANR_HIP(hipEventRecord(e[i], st));
-    return ANR_OK;
-  }
-  ~Events() {
-    for (auto &x : e)
-      if (x) (void)hipEventDestroy(x);
-  }
-};
-
-int grow(void **p, size_t *cap, size_t need, const char *what) {
-  if (need <= *cap) return ANR_OK;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const size_t want = need + need / 4;
-  if (hipMalloc(p, want) != hipSuccess) {
-    *p = nullptr;
-    (void)hipGetLastError();
-    return fail(ANR_EHIP, "diversify: could not allocate %zu bytes of device memory for %s", want, what);
-  }
-  *cap = want;
-  return ANR_OK;
-}
-
 // byte offsets of the arrays of one call inside the arena, every one 8-byte aligned
 struct Layout {
   size_t offs, soff, koff, rows, score, types, rowq, tiles, in_end;  // inputs: one copy to the device
@@ -395,11 +323,10 @@ struct Layout {
   size_t kept, sel, n_kept, n_sel, sel_sim, out_end;                 // outputs: one copy back
 };
 
-size_t al8(size_t x) { return (x + 7) & ~(size_t)7; }
-
-int run(anr_diversity *d, const float *x32, int dim, int64_t ntotal, int64_t nq, const int64_t *offs, const int64_t *rows,
-        const double *sim_host, const double *scores, const uint32_t *types, const anr_diversity_params &prm, int32_t *kept,
-        int32_t *n_kept, int32_t *selected, int32_t *n_selected, double *sel_sim, hipStream_t st) {
+int run(DevBuf<unsigned char> &sim_buf, DevBuf<unsigned char> &arena, const float *x32, int dim, int64_t ntotal, int64_t nq,
+        const int64_t *offs, const int64_t *rows, const double *sim_host, const double *scores, const uint32_t *types,
+        const anr_diversity_params &prm, int32_t *kept, int32_t *n_kept, int32_t *selected, int32_t *n_selected,
+        double *sel_sim, hipStream_t st) {
   const int64_t total = offs[nq];
   std::vector<int64_t> soff((size_t)nq), koff((size_t)nq);
   std::vector<int> tiles;
@@ -426,32 +353,29 @@ int run(anr_diversity *d, const float *x32, int dim, int64_t ntotal, int64_t nq,
     return fail(ANR_EINVAL, "diversify: too many queries or candidates for one call");
 
   Layout L{};
-  size_t at = 0;
-  auto take = [&](size_t bytes) {
-    const size_t r = at;
-    at = al8(at + bytes);
-    return r;
-  };
-  L.offs = take((size_t)(nq + 1) * 8);
-  L.soff = take((size_t)nq * 8);
-  L.koff = take((size_t)nq * 8);
-  L.rows = take(sim_host ? 0 : (size_t)total * 8);
-  L.score = take((size_t)total * 8);
-  L.types = take(types ? (size_t)total * 4 : 0);
-  L.rowq = take(sim_host ? 0 : (size_t)total * 4);
-  L.tiles = take(tiles.size() * 4);
-  L.in_end = at;
-  L.nrm = take((size_t)total * 8);
-  L.kept = take((size_t)total * 4);
-  L.sel = take((size_t)total * 4);
-  L.n_kept = take((size_t)nq * 4);
-  L.n_sel = take((size_t)nq * 4);
-  L.sel_sim = take((size_t)ktotal * 8);
-  L.out_end = at;
+  ArenaLayout<8> lay;
+  L.offs = lay.take((size_t)(nq + 1) * 8);
+  L.soff = lay.take((size_t)nq * 8);
+  L.koff = lay.take((size_t)nq * 8);
+  L.rows = lay.take(sim_host ? 0 : (size_t)total * 8);
+  L.score = lay.take((size_t)total * 8);
+  L.types = lay.take(types ? (size_t)total * 4 : 0);
+  L.rowq = lay.take(sim_host ? 0 : (size_t)total * 4);
+  L.tiles = lay.take(tiles.size() * 4);
+  L.in_end = lay.at;
+  L.nrm = lay.take((size_t)total * 8);
+  L.kept = lay.take((size_t)total * 4);
+  L.sel = lay.take((size_t)total * 4);
+  L.n_kept = lay.take((size_t)nq * 4);
+  L.n_sel = lay.take((size_t)nq * 4);
+  L.sel_sim = lay.take((size_t)ktotal * 8);
+  L.out_end = lay.at;
 
-  ANR_TRY(grow(&d->arena, &d->arena_cap, L.out_end, "the candidate arrays"));
-  ANR_TRY(grow(&d->sim, &d->sim_cap, (size_t)stotal * 8, "the similarity matrices"));
-  unsigned char *A = static_cast<unsigned char *>(d->arena);
+  // both grow by a quarter beyond the need
+  ANR_TRY(arena.alloc((int64_t)L.out_end, "diversify", (int64_t)(L.out_end + L.out_end / 4), "the candidate arrays"));
+  ANR_TRY(sim_buf.alloc(stotal * 8, "diversify", stotal * 10, "the similarity matrices"));
+  unsigned char *A = arena.p;
+  double *sim = reinterpret_cast<double *>(sim_buf.p);
 
   std::vector<unsigned char> in(L.in_end, 0);
   memcpy(&in[L.offs], offs, (size_t)(nq + 1) * 8);
@@ -466,14 +390,14 @@ int run(anr_diversity *d, const float *x32, int dim, int64_t ntotal, int64_t nq,
       for (int64_t c = offs[q]; c < offs[q + 1]; ++c) rowq[c] = (int)q;
     if (!tiles.empty()) memcpy(&in[L.tiles], tiles.data(), tiles.size() * 4);
   }
-  Events ev;
+  Events<5> ev;
   if (g_timing) ANR_TRY(ev.init());
   ANR_TRY(ev.mark(0, st));
   ANR_HIP(hipMemcpyAsync(A, in.data(), L.in_end, hipMemcpyHostToDevice, st));
 
   ANR_TRY(ev.mark(1, st));
   if (sim_host) {
-    ANR_HIP(hipMemcpyAsync(d->sim, sim_host, (size_t)stotal * 8, hipMemcpyHostToDevice, st));
+    ANR_HIP(hipMemcpyAsync(sim, sim_host, (size_t)stotal * 8, hipMemcpyHostToDevice, st));
   } else {
     DivGram g{x32,
               dim,
@@ -481,7 +405,7 @@ int run(anr_diversity *d, const float *x32, int dim, int64_t ntotal, int64_t nq,
               reinterpret_cast<const int64_t *>(A + L.offs),
               reinterpret_cast<const int64_t *>(A + L.soff),
               reinterpret_cast<const int *>(A + L.tiles),
-              static_cast<double *>(d->sim),
+              sim,
               reinterpret_cast<double *>(A + L.nrm)};
     hipLaunchKernelGGL(k_div_gram, dim3((unsigned)n_tiles), dim3(kDivNT), 0, st, g);
     ANR_HIP(hipGetLastError());
@@ -492,7 +416,7 @@ int run(anr_diversity *d, const float *x32, int dim, int64_t ntotal, int64_t nq,
 
   ANR_TRY(ev.mark(2, st));
   DivSelect s{};
-  s.sim = static_cast<const double *>(d->sim);
+  s.sim = sim;
   s.offs = reinterpret_cast<const int64_t *>(A + L.offs);
   s.soff = reinterpret_cast<const int64_t *>(A + L.soff);
   s.koff = reinterpret_cast<const int64_t *>(A + L.koff);
@@ -513,9 +437,9 @@ int run(anr_diversity *d, const float *x32, int dim, int64_t ntotal, int64_t nq,
   ANR_TRY(ev.mark(4, st));
   ANR_HIP(hipStreamSynchronize(st));
   if (ev.on) {
-    ANR_HIP(hipEventElapsedTime(&g_times[0], ev.e[1], ev.e[2]));
-    ANR_HIP(hipEventElapsedTime(&g_times[1], ev.e[2], ev.e[3]));
-    ANR_HIP(hipEventElapsedTime(&g_times[2], ev.e[0], ev.e[4]));
+    ANR_TRY(ev.elapsed(1, 2, &g_times[0]));
+    ANR_TRY(ev.elapsed(2, 3, &g_times[1]));
+    ANR_TRY(ev.elapsed(0, 4, &g_times[2]));
   }
   const unsigned char *O = out.data() - L.kept;
   for (int64_t q = 0; q < nq; ++q) {
@@ -567,12 +491,9 @@ extern "C" int anr_index_diversify(anr_index *h, int32_t device, int64_t nq, con
   if (!h) {
     DeviceGuard g(device);
     if (!g.ok) return fail(ANR_EHIP, "hipSetDevice(%d) failed", device);
-    anr_diversity local;
-    const int rc = run(&local, nullptr, 0, 0, nq, offs, nullptr, sim_host, scores_host, type_masks_host, *p, kept, n_kept,
-                       selected, n_selected, sel_sim, nullptr);
-    if (local.sim) (void)hipFree(local.sim);
-    if (local.arena) (void)hipFree(local.arena);
-    return rc;
+    DevBuf<unsigned char> sim, arena;  // of this call only
+    return run(sim, arena, nullptr, 0, 0, nq, offs, nullptr, sim_host, scores_host, type_masks_host, *p, kept, n_kept, selected,
+               n_selected, sel_sim, nullptr);
   }
   const IndexCore c = index_core(h);
   DeviceGuard g(c.device);
@@ -583,8 +504,7 @@ extern "C" int anr_index_diversify(anr_index *h, int32_t device, int64_t nq, con
     for (int64_t e = 0; e < total; ++e)
       if (rows_host[e] < 0 || rows_host[e] >= cur.ntotal)
         return fail(ANR_EINVAL, "diversify: row id %lld outside [0, %lld)", (long long)rows_host[e], (long long)cur.ntotal);
-  anr_diversity *&d = index_diversity(h);
-  if (!d) d = new anr_diversity();
-  return run(d, cur.x32, cur.dim, cur.ntotal, nq, offs, rows_host, sim_host, scores_host, type_masks_host, *p, kept, n_kept,
-             selected, n_selected, sel_sim, cur.stream);
+  IndexScratch &sc = index_scratch(h);
+  return run(sc.div_sim, sc.div_arena, cur.x32, cur.dim, cur.ntotal, nq, offs, rows_host, sim_host, scores_host,
+             type_masks_host, *p, kept, n_kept, selected, n_selected, sel_sim, cur.stream);
 }

@@ -476,16 +476,15 @@ struct anr_graph {
   int R = 64, K = 128;           // of the current graph / the next rebuild
   int64_t n = 0;
   int dimp = 0;
-  int *adj = nullptr;            // device [n][R]
-  signed char *codes = nullptr;  // device [n][dimp]
-  int *rexp = nullptr, *rsq = nullptr;
+  DevBuf<int> adj;            // device [n][R]
+  DevBuf<signed char> codes;  // device [n][dimp]
+  DevBuf<int> rexp, rsq;
   bool keep_knn = false;         // keep the pre-prune lists of every build (tests): n * K int32 of host memory
   std::vector<int> knn;          // host [n][K]: those lists (empty unless keep_knn, and after graph_set)
   // per-search scratch
-  float *q = nullptr, *D = nullptr;
-  int64_t *I = nullptr;
-  int *qstat = nullptr;
-  int64_t q_cap = 0, out_cap = 0;
+  DevBuf<float> q, D;
+  DevBuf<int64_t> I;
+  DevBuf<int> qstat;
   std::vector<int> qstat_host;
   anr_graph_stats st{};
 };
@@ -497,20 +496,12 @@ void graph_mark_stale(anr_graph *g) {
 }
 
 static void free_storage(anr_graph *g) {
-  for (void *p : {(void *)g->adj, (void *)g->codes, (void *)g->rexp, (void *)g->rsq})
-    if (p) (void)hipFree(p);
-  g->adj = nullptr;
-  g->codes = nullptr;
-  g->rexp = g->rsq = nullptr;
+  g->adj.release(), g->codes.release(), g->rexp.release(), g->rsq.release();
   g->has = false;
 }
 
 void graph_free(anr_graph *g) {
-  if (!g) return;
-  free_storage(g);
-  for (void *p : {(void *)g->q, (void *)g->D, (void *)g->I, (void *)g->qstat})
-    if (p) (void)hipFree(p);
-  delete g;
+  delete g;  // on the index's device: anr_index_destroy calls this under its guard
 }
 
 }  // namespace anr
@@ -567,24 +558,17 @@ void prune_host(const std::vector<int> &F, int64_t n, int K, int R, std::vector<
   }
 }
 
-template <typename T>
-int dalloc(T **p, int64_t count) {
-  *p = nullptr;
-  ANR_HIP(hipMalloc(reinterpret_cast<void **>(p), (size_t)std::max<int64_t>(count, 1) * sizeof(T)));
-  return ANR_OK;
-}
-
 // the traversal image of the current rows (caller holds g->mu)
 int build_image(anr_index *h, anr_graph *g) {
   IndexCore c = index_core(h);
   std::lock_guard<std::mutex> lk(*c.mu);
   const int64_t n = c.ntotal;
   g->dimp = (int)round_up(c.dim, 16);
-  ANR_TRY(dalloc(&g->codes, n * g->dimp));
-  ANR_TRY(dalloc(&g->rexp, n));
-  ANR_TRY(dalloc(&g->rsq, n));
+  ANR_TRY(g->codes.alloc(n * g->dimp, "graph"));
+  ANR_TRY(g->rexp.alloc(n, "graph"));
+  ANR_TRY(g->rsq.alloc(n, "graph"));
   if (n > 0) {
-    ImageParams ip{c.x32, n, c.dim, g->dimp, g->codes, g->rexp, g->rsq};
+    ImageParams ip{c.x32, n, c.dim, g->dimp, g->codes.p, g->rexp.p, g->rsq.p};
     hipLaunchKernelGGL(k_graph_image, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, c.stream, ip);
     ANR_HIP(hipGetLastError());
   }
@@ -605,21 +589,21 @@ int build_locked(anr_index *h, anr_graph *g, int R, int K) {
   g->stale = false;
   auto t0 = std::chrono::steady_clock::now();
   // kNN lists: the exact streaming search of the index itself, chunk by chunk
-  int *lists = nullptr, *F = nullptr;
-  float *Dk = nullptr;
-  int64_t *Ik = nullptr;
+  DevBuf<int> lists, F;  // these four are released before the graph itself is allocated
+  DevBuf<float> Dk;
+  DevBuf<int64_t> Ik;
   const int K1 = K + 1;
   const int64_t chunk = std::min<int64_t>(kKnnChunk, std::max<int64_t>(n, 1));
-  int rc = dalloc(&lists, n * K);
-  if (rc == ANR_OK) rc = dalloc(&F, n * K);
-  if (rc == ANR_OK) rc = dalloc(&Dk, chunk * K1);
-  if (rc == ANR_OK) rc = dalloc(&Ik, chunk * K1);
+  int rc = lists.alloc(n * K, "graph");
+  if (rc == ANR_OK) rc = F.alloc(n * K, "graph");
+  if (rc == ANR_OK) rc = Dk.alloc(chunk * K1, "graph");
+  if (rc == ANR_OK) rc = Ik.alloc(chunk * K1, "graph");
   for (int64_t i0 = 0; i0 < n && rc == ANR_OK; i0 += chunk) {
     const int64_t m = std::min(chunk, n - i0);
-    rc = anr_index_search_dev_async(h, c.x32 + i0 * c.dim, m, K1, Dk, Ik, nullptr);
+    rc = anr_index_search_dev_async(h, c.x32 + i0 * c.dim, m, K1, Dk.p, Ik.p, nullptr);
     if (rc == ANR_OK) rc = anr_index_sync(h);
     if (rc != ANR_OK) break;
-    KnnListParams kp{Ik, i0, m, c.id_offset, K, lists};
+    KnnListParams kp{Ik.p, i0, m, c.id_offset, K, lists.p};
     hipLaunchKernelGGL(k_knn_lists, dim3((unsigned)ceil_div(m, 256)), dim3(256), 0, c.stream, kp);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
@@ -629,26 +613,25 @@ int build_locked(anr_index *h, anr_graph *g, int R, int K) {
   auto t1 = std::chrono::steady_clock::now();
   std::vector<int> Fh, adj;
   if (rc == ANR_OK && n > 0) {
-    DetourParams dp{lists, n, K, F};
+    DetourParams dp{lists.p, n, K, F.p};
     hipLaunchKernelGGL(k_detour_order, dim3((unsigned)n), dim3(256), 0, c.stream, dp);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
     Fh.resize(n * K);
-    if (e == hipSuccess) e = hipMemcpy(Fh.data(), F, (size_t)n * K * sizeof(int), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(Fh.data(), F.p, (size_t)n * K * sizeof(int), hipMemcpyDeviceToHost);
     if (g->keep_knn) {
       g->knn.resize(n * K);
-      if (e == hipSuccess) e = hipMemcpy(g->knn.data(), lists, (size_t)n * K * sizeof(int), hipMemcpyDeviceToHost);
+      if (e == hipSuccess) e = hipMemcpy(g->knn.data(), lists.p, (size_t)n * K * sizeof(int), hipMemcpyDeviceToHost);
     }
     if (e != hipSuccess) rc = fail(ANR_EHIP, "graph prune failed: %s", hipGetErrorString(e));
   }
-  for (void *p : {(void *)lists, (void *)F, (void *)Dk, (void *)Ik})
-    if (p) (void)hipFree(p);
+  lists.release(), F.release(), Dk.release(), Ik.release();
   if (rc == ANR_OK) {
     prune_host(Fh, n, K, R, adj);
     Fh.clear();
-    rc = dalloc(&g->adj, n * R);
+    rc = g->adj.alloc(n * R, "graph");
     if (rc == ANR_OK && n > 0 &&
-        hipMemcpy(g->adj, adj.data(), (size_t)n * R * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
+        hipMemcpy(g->adj.p, adj.data(), (size_t)n * R * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
       rc = fail(ANR_EHIP, "uploading the graph failed");
   }
   const double prune_ms = ms_since(t1);
@@ -696,45 +679,26 @@ int search_impl(anr_index *h, const float *q, bool q_host, int64_t nq, int32_t k
     }
     return ANR_OK;
   }
-  if (q_host && nq * c.dim > g->q_cap) {
-    if (g->q) (void)hipFree(g->q);
-    g->q = nullptr;
-    g->q_cap = 0;
-    ANR_TRY(dalloc(&g->q, nq * c.dim));
-    g->q_cap = nq * c.dim;
-  }
-  if (nq * k > g->out_cap) {
-    for (void *p : {(void *)g->D, (void *)g->I})
-      if (p) (void)hipFree(p);
-    g->D = nullptr;
-    g->I = nullptr;
-    g->out_cap = 0;
-    ANR_TRY(dalloc(&g->D, nq * k));
-    ANR_TRY(dalloc(&g->I, nq * k));
-    g->out_cap = nq * k;
-  }
-  if (nq * 3 > (int64_t)g->qstat_host.size()) {
-    if (g->qstat) (void)hipFree(g->qstat);
-    g->qstat = nullptr;
-    g->qstat_host.clear();
-    ANR_TRY(dalloc(&g->qstat, nq * 3));
-    g->qstat_host.resize(nq * 3);
-  }
+  if (q_host) ANR_TRY(g->q.alloc(nq * c.dim, "graph"));
+  ANR_TRY(g->D.alloc(nq * k, "graph"));
+  ANR_TRY(g->I.alloc(nq * k, "graph"));
+  ANR_TRY(g->qstat.alloc(nq * 3, "graph"));
+  if (nq * 3 > (int64_t)g->qstat_host.size()) g->qstat_host.resize(nq * 3);
   std::lock_guard<std::mutex> lk(*c.mu);
   const float *qd = q;
   if (q_host) {
-    ANR_HIP(hipMemcpyAsync(g->q, q, (size_t)nq * c.dim * sizeof(float), hipMemcpyHostToDevice, c.stream));
-    qd = g->q;
+    ANR_HIP(hipMemcpyAsync(g->q.p, q, (size_t)nq * c.dim * sizeof(float), hipMemcpyHostToDevice, c.stream));
+    qd = g->q.p;
   }
   int efp = 64;
   while (efp < std::max(k, ef)) efp <<= 1;
   SearchParams sp{};
   sp.q = qd;
   sp.x32 = c.x32;
-  sp.codes = g->codes;
-  sp.rexp = g->rexp;
-  sp.rsq = g->rsq;
-  sp.adj = g->adj;
+  sp.codes = g->codes.p;
+  sp.rexp = g->rexp.p;
+  sp.rsq = g->rsq.p;
+  sp.adj = g->adj.p;
   sp.n = n;
   sp.id_offset = c.id_offset;
   sp.dim = c.dim;
@@ -746,14 +710,14 @@ int search_impl(anr_index *h, const float *q, bool q_host, int64_t nq, int32_t k
   sp.max_iter = efp;
   sp.metric = c.metric;
   sp.normalize = c.normalize;
-  sp.D = g->D;
-  sp.I = g->I;
-  sp.qstat = g->qstat;
+  sp.D = g->D.p;
+  sp.I = g->I.p;
+  sp.qstat = g->qstat.p;
   hipLaunchKernelGGL(k_graph_search, dim3((unsigned)nq), dim3(256), 0, c.stream, sp);
   ANR_HIP(hipGetLastError());
-  ANR_HIP(hipMemcpyAsync(D, g->D, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, c.stream));
-  ANR_HIP(hipMemcpyAsync(I, g->I, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, c.stream));
-  ANR_HIP(hipMemcpyAsync(g->qstat_host.data(), g->qstat, (size_t)nq * 3 * sizeof(int), hipMemcpyDeviceToHost, c.stream));
+  ANR_HIP(hipMemcpyAsync(D, g->D.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, c.stream));
+  ANR_HIP(hipMemcpyAsync(I, g->I.p, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, c.stream));
+  ANR_HIP(hipMemcpyAsync(g->qstat_host.data(), g->qstat.p, (size_t)nq * 3 * sizeof(int), hipMemcpyDeviceToHost, c.stream));
   ANR_HIP(hipStreamSynchronize(c.stream));
   for (int64_t i = 0; i < nq; ++i) {
     g->st.last_iterations += g->qstat_host[i * 3];
@@ -797,7 +761,7 @@ int anr_index_graph_get(anr_index *h, int32_t *adj, int64_t n, int32_t R) {
   ANR_TRY(ensure_fresh(h, g));
   if (n != g->n || R != g->R)
     return fail(ANR_EINVAL, "buffer of [%lld][%d] for a graph of [%lld][%d]", (long long)n, R, (long long)g->n, g->R);
-  if (g->n > 0) ANR_HIP(hipMemcpy(adj, g->adj, (size_t)g->n * g->R * sizeof(int), hipMemcpyDeviceToHost));
+  if (g->n > 0) ANR_HIP(hipMemcpy(adj, g->adj.p, (size_t)g->n * g->R * sizeof(int), hipMemcpyDeviceToHost));
   return ANR_OK;
 }
 
@@ -817,8 +781,8 @@ int anr_index_graph_set(anr_index *h, const int32_t *adj, int64_t n, int32_t R) 
   g->R = R;
   g->n = n;
   g->stale = false;
-  ANR_TRY(dalloc(&g->adj, n * R));
-  if (n > 0) ANR_HIP(hipMemcpy(g->adj, adj, (size_t)n * R * sizeof(int), hipMemcpyHostToDevice));
+  ANR_TRY(g->adj.alloc(n * R, "graph"));
+  if (n > 0) ANR_HIP(hipMemcpy(g->adj.p, adj, (size_t)n * R * sizeof(int), hipMemcpyHostToDevice));
   ANR_TRY(build_image(h, g));
   g->has = true;
   return ANR_OK;
@@ -848,24 +812,19 @@ int anr_index_graph_image(anr_index *h, const int64_t *ids, int64_t n, float *ou
     if (ids[j] < 0 || ids[j] >= g->n) return fail(ANR_EINVAL, "id %lld not in the index", (long long)ids[j]);
   if (n == 0) return ANR_OK;
   IndexCore c = index_core(h);
-  int64_t *di = nullptr;
-  float *dout = nullptr;
-  int rc = dalloc(&di, n);
-  if (rc == ANR_OK) rc = dalloc(&dout, n * c.dim);
-  hipError_t e = hipSuccess;
-  if (rc == ANR_OK) {
-    e = hipMemcpy(di, ids, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice);
-    DecodeParams dp{g->codes, g->rexp, di, n, c.dim, g->dimp, dout};
-    if (e == hipSuccess)
-      hipLaunchKernelGGL(k_graph_decode, dim3((unsigned)ceil_div(n * c.dim, 256)), dim3(256), 0, c.stream, dp);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
-    if (e == hipSuccess) e = hipMemcpy(out, dout, (size_t)n * c.dim * sizeof(float), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = fail(ANR_EHIP, "decoding the traversal image failed: %s", hipGetErrorString(e));
-  }
-  if (di) (void)hipFree(di);
-  if (dout) (void)hipFree(dout);
-  return rc;
+  DevBuf<int64_t> di;  // of this call
+  DevBuf<float> dout;
+  ANR_TRY(di.alloc(n, "graph"));
+  ANR_TRY(dout.alloc(n * c.dim, "graph"));
+  hipError_t e = hipMemcpy(di.p, ids, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice);
+  DecodeParams dp{g->codes.p, g->rexp.p, di.p, n, c.dim, g->dimp, dout.p};
+  if (e == hipSuccess)
+    hipLaunchKernelGGL(k_graph_decode, dim3((unsigned)ceil_div(n * c.dim, 256)), dim3(256), 0, c.stream, dp);
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+  if (e == hipSuccess) e = hipMemcpy(out, dout.p, (size_t)n * c.dim * sizeof(float), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail(ANR_EHIP, "decoding the traversal image failed: %s", hipGetErrorString(e));
+  return ANR_OK;
 }
 
 int anr_index_graph_stats(anr_index *h, anr_graph_stats *out) {

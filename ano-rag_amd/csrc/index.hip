@@ -19,10 +19,7 @@
 #include <vector>
 
 #include "cluster.hpp"
-#include "cluster_quality.hpp"
-#include "kmeans.hpp"
 #include "common.hpp"
-#include "diversity.hpp"
 #include "graph.hpp"
 #include "index_kernels.hpp"
 #include "tiny_kernels.hpp"
@@ -160,9 +157,7 @@ struct anr_index {
 
   anr_search_stats stats{};
   anr_graph *graph = nullptr;  // graph index on these rows (graph.hip); adds and resets mark it stale
-  anr_diversity *diversity = nullptr;  // scratch of anr_index_diversify (diversity.hip)
-  anr_cluster_quality *cluster_quality = nullptr;  // scratch of anr_index_cluster_quality (cluster_quality.hip)
-  anr_kmeans *kmeans = nullptr;  // scratch of anr_index_kmeans (kmeans.hip)
+  IndexScratch scratch;        // arenas of diversity.hip, cluster_quality.hip and kmeans.hip (graph.hpp)
 };
 
 namespace {
@@ -1596,9 +1591,7 @@ int anr_index_destroy(anr_index *h) {
   dev_free(h->tiny_ticket);
   dev_free(h->tiny_stamps);
   graph_free(h->graph);
-  diversity_free(h->diversity);
-  cluster_quality_free(h->cluster_quality);
-  kmeans_free(h->kmeans);
+  h->scratch = IndexScratch{};
   for (auto &e : h->ev_call)
     if (e) (void)hipEventDestroy(e);
   for (hipStream_t s : {h->bstream[0], h->bstream[1], h->bstream[2], h->stream})
@@ -2150,11 +2143,7 @@ IndexCore index_core(anr_index *h) {
 
 anr_graph *&index_graph(anr_index *h) { return h->graph; }
 
-anr_diversity *&index_diversity(anr_index *h) { return h->diversity; }
-
-anr_cluster_quality *&index_cluster_quality(anr_index *h) { return h->cluster_quality; }
-
-anr_kmeans *&index_kmeans(anr_index *h) { return h->kmeans; }
+IndexScratch &index_scratch(anr_index *h) { return h->scratch; }
 
 int index_join_view(anr_index *h, JoinView *out) {
   ANR_TRY(drain(h));

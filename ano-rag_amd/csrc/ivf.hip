@@ -861,36 +861,12 @@ __global__ __launch_bounds__(1024) void k_pq_select(const float *keys, const int
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 
+// room for n elements in a buffer that grows by half beyond what it holds, so that adds in chunks do not reallocate
+// every time
 template <typename T>
-static int dev_grow(T **p, int64_t *cap, int64_t need) {
-  if (need <= *cap && *p) return ANR_OK;
-  int64_t nc = std::max<int64_t>(need, *cap + *cap / 2);
-  nc = std::max<int64_t>(nc, 1);
-  if (*p) ANR_HIP(hipFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  ANR_HIP(hipMalloc((void **)p, (size_t)nc * sizeof(T)));
-  *cap = nc;
-  return ANR_OK;
+static int need(DevBuf<T> &b, int64_t n) {
+  return b.alloc(n, "ivf", b.cap + b.cap / 2);
 }
-
-template <typename T>
-static void dev_free(T *&p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
-
-// a device buffer with its capacity
-template <typename T>
-struct Buf {
-  T *p = nullptr;
-  int64_t cap = 0;
-  int need(int64_t n) { return dev_grow(&p, &cap, n); }
-  void release() {
-    dev_free(p);
-    cap = 0;
-  }
-};
 
 static uint64_t splitmix(uint64_t &s) {
   uint64_t z = (s += 0x9e3779b97f4a7c15ull);
@@ -910,46 +886,46 @@ struct anr_ivf {
   hipStream_t stream = nullptr;
   std::mutex mu;
   bool trained = false;
-  Buf<float> cent, cn2, cnrm;
+  DevBuf<float> cent, cn2, cnrm;
   float cmax = 0.0f;
   // every row ever added, by global id
-  Buf<float> xall, xnrm;
-  Buf<int32_t> assign;
-  Buf<uint8_t> alive_d;
+  DevBuf<float> xall, xnrm;
+  DevBuf<int32_t> assign;
+  DevBuf<uint8_t> alive_d;
   std::vector<uint8_t> alive;
   int64_t n_all = 0, n_alive = 0;
   float max_norm = 0.0f;
   // list-ordered copy
-  Buf<float> xs;
-  Buf<__half> x16;
-  Buf<int64_t> ids;
-  Buf<double> n2;
+  DevBuf<float> xs;
+  DevBuf<__half> x16;
+  DevBuf<int64_t> ids;
+  DevBuf<double> n2;
   std::vector<int64_t> list_cnt, list_off;  // alive rows per list; first padded row per list (nlist + 1 entries)
   // scratch
-  Buf<unsigned long long> skeys, skeys2;
-  Buf<unsigned> svals, svals2;
-  Buf<char> stemp;
-  Buf<int32_t> counts, fix, nfix;
-  Buf<int64_t> seg, off_d;
-  Buf<float> qbuf, qnrm, qn2, qbound, ckey, Dd;
-  Buf<double> cs;
-  Buf<int32_t> probe, cpos, failq, qlist;
-  Buf<int64_t> cbase, ctot, eoff, Id, rid;
-  Buf<float> rout;
-  Buf<int32_t> eq;
-  Buf<ProbeItem> items;
+  DevBuf<unsigned long long> skeys, skeys2;
+  DevBuf<unsigned> svals, svals2;
+  DevBuf<char> stemp;
+  DevBuf<int32_t> counts, fix, nfix;
+  DevBuf<int64_t> seg, off_d;
+  DevBuf<float> qbuf, qnrm, qn2, qbound, ckey, Dd;
+  DevBuf<double> cs;
+  DevBuf<int32_t> probe, cpos, failq, qlist;
+  DevBuf<int64_t> cbase, ctot, eoff, Id, rid;
+  DevBuf<float> rout;
+  DevBuf<int32_t> eq;
+  DevBuf<ProbeItem> items;
   std::vector<float> host_tmp;
   // product quantiser (pq): the rows, their lists and codes live on the host in insertion order; the device keeps the
   // codebooks and the list-ordered codes (lcodes) with their ids
   bool pq = false, pq_ready = false;  // PQ mode; codebooks present
   int m = 0, m4 = 0, dsub = 0;         // sub-spaces, code dwords per row, values per sub-space
-  Buf<float> cb, cbn2, cbnrm, cbmax;   // [m][256][dsub]; |entry|^2, |entry|; per sub-space max |entry| (the bound)
+  DevBuf<float> cb, cbn2, cbnrm, cbmax;   // [m][256][dsub]; |entry|^2, |entry|; per sub-space max |entry| (the bound)
   std::vector<float> xh;
   std::vector<int32_t> assign_h;
   std::vector<uint8_t> codes_h;        // [n_all][m]
-  Buf<uint32_t> lcodes;
-  Buf<float> lut;
-  Buf<PqItem> pitems;
+  DevBuf<uint32_t> lcodes;
+  DevBuf<float> lut;
+  DevBuf<PqItem> pitems;
 };
 
 namespace {
@@ -986,8 +962,8 @@ int update_cstats(anr_ivf *h) {
 // list of each of n preprocessed rows x (norms xn) -> out
 int assign_rows(anr_ivf *h, const float *x, const float *xn, int64_t n, int32_t *out) {
   if (n == 0) return ANR_OK;
-  ANR_TRY(h->fix.need(n));
-  ANR_TRY(h->nfix.need(1));
+  ANR_TRY(need(h->fix, n));
+  ANR_TRY(need(h->nfix, 1));
   ANR_HIP(hipMemsetAsync(h->nfix.p, 0, 4, h->stream));
   const int l2 = h->metric == ANR_METRIC_L2;
   hipLaunchKernelGGL(k_ivf_assign, dim3((unsigned)ceil_div(n, 64)), dim3(256), 0, h->stream, x, n, h->dim, h->cent.p,
@@ -1006,12 +982,12 @@ int assign_rows(anr_ivf *h, const float *x, const float *xn, int64_t n, int32_t 
 
 // stable sort of rows [0, n) by list (dead rows last); counts per list to `cnt`
 int sort_by_list(anr_ivf *h, const int32_t *assign, const uint8_t *alive, int64_t n, std::vector<int64_t> &cnt) {
-  ANR_TRY(h->skeys.need(n));
-  ANR_TRY(h->skeys2.need(n));
-  ANR_TRY(h->svals.need(n));
-  ANR_TRY(h->svals2.need(n));
-  ANR_TRY(h->stemp.need((int64_t)radix_sort_temp_bytes(n)));
-  ANR_TRY(h->counts.need(h->nlist + 1));
+  ANR_TRY(need(h->skeys, n));
+  ANR_TRY(need(h->skeys2, n));
+  ANR_TRY(need(h->svals, n));
+  ANR_TRY(need(h->svals2, n));
+  ANR_TRY(need(h->stemp, (int64_t)radix_sort_temp_bytes(n)));
+  ANR_TRY(need(h->counts, h->nlist + 1));
   ANR_HIP(hipMemsetAsync(h->counts.p, 0, (size_t)(h->nlist + 1) * 4, h->stream));
   hipLaunchKernelGGL(k_ivf_keys, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, h->stream, assign, alive, n, h->nlist,
                      h->skeys.p, h->svals.p, h->counts.p);
@@ -1039,11 +1015,11 @@ int rebuild(anr_ivf *h) {
   }
   const int64_t npad = std::max<int64_t>(h->list_off[nl], kTile);
   const int dim = h->dim;
-  ANR_TRY(h->xs.need(npad * dim));
-  ANR_TRY(h->x16.need(npad * dim));
-  ANR_TRY(h->ids.need(npad));
-  ANR_TRY(h->n2.need(npad));
-  ANR_TRY(h->off_d.need(2 * nl));
+  ANR_TRY(need(h->xs, npad * dim));
+  ANR_TRY(need(h->x16, npad * dim));
+  ANR_TRY(need(h->ids, npad));
+  ANR_TRY(need(h->n2, npad));
+  ANR_TRY(need(h->off_d, 2 * nl));
   ANR_HIP(hipMemsetAsync(h->xs.p, 0, (size_t)npad * dim * 4, h->stream));
   ANR_HIP(hipMemsetAsync(h->x16.p, 0, (size_t)npad * dim * 2, h->stream));
   ANR_HIP(hipMemsetAsync(h->ids.p, 0xff, (size_t)npad * 8, h->stream));  // -1
@@ -1084,32 +1060,24 @@ int grow_all(anr_ivf *h, int64_t n_new) {
   const int64_t need = h->n_all + n_new;
   if (need <= h->xall.cap / h->dim && h->xall.p) return ANR_OK;
   const int64_t cap = std::max<int64_t>(need, h->n_all + h->n_all / 2);
-  float *nx = nullptr, *nn = nullptr;
-  int32_t *na = nullptr;
-  uint8_t *nal = nullptr;
-  ANR_HIP(hipMalloc((void **)&nx, (size_t)cap * h->dim * 4));
-  ANR_HIP(hipMalloc((void **)&nn, (size_t)cap * 4));
-  ANR_HIP(hipMalloc((void **)&na, (size_t)cap * 4));
-  ANR_HIP(hipMalloc((void **)&nal, (size_t)cap));
+  DevBuf<float> nx, nn;
+  DevBuf<int32_t> na;
+  DevBuf<uint8_t> nal;
+  ANR_TRY(nx.alloc(cap * h->dim, "ivf"));
+  ANR_TRY(nn.alloc(cap, "ivf"));
+  ANR_TRY(na.alloc(cap, "ivf"));
+  ANR_TRY(nal.alloc(cap, "ivf"));
   if (h->n_all > 0) {
-    ANR_HIP(hipMemcpyAsync(nx, h->xall.p, (size_t)h->n_all * h->dim * 4, hipMemcpyDeviceToDevice, h->stream));
-    ANR_HIP(hipMemcpyAsync(nn, h->xnrm.p, (size_t)h->n_all * 4, hipMemcpyDeviceToDevice, h->stream));
-    ANR_HIP(hipMemcpyAsync(na, h->assign.p, (size_t)h->n_all * 4, hipMemcpyDeviceToDevice, h->stream));
-    ANR_HIP(hipMemcpyAsync(nal, h->alive_d.p, (size_t)h->n_all, hipMemcpyDeviceToDevice, h->stream));
+    ANR_HIP(hipMemcpyAsync(nx.p, h->xall.p, (size_t)h->n_all * h->dim * 4, hipMemcpyDeviceToDevice, h->stream));
+    ANR_HIP(hipMemcpyAsync(nn.p, h->xnrm.p, (size_t)h->n_all * 4, hipMemcpyDeviceToDevice, h->stream));
+    ANR_HIP(hipMemcpyAsync(na.p, h->assign.p, (size_t)h->n_all * 4, hipMemcpyDeviceToDevice, h->stream));
+    ANR_HIP(hipMemcpyAsync(nal.p, h->alive_d.p, (size_t)h->n_all, hipMemcpyDeviceToDevice, h->stream));
     ANR_HIP(hipStreamSynchronize(h->stream));
   }
-  h->xall.release();
-  h->xnrm.release();
-  h->assign.release();
-  h->alive_d.release();
-  h->xall.p = nx;
-  h->xall.cap = cap * h->dim;
-  h->xnrm.p = nn;
-  h->xnrm.cap = cap;
-  h->assign.p = na;
-  h->assign.cap = cap;
-  h->alive_d.p = nal;
-  h->alive_d.cap = cap;
+  h->xall = std::move(nx);  // the old blocks are freed here
+  h->xnrm = std::move(nn);
+  h->assign = std::move(na);
+  h->alive_d = std::move(nal);
   return ANR_OK;
 }
 
@@ -1137,10 +1105,10 @@ int add_impl(anr_ivf *h, const float *x, int64_t n, bool host) {
 }
 
 // Lloyd's iterations over m preprocessed rows at h->xall-like buffer x (norms xn), from the current centroids
-int lloyd(anr_ivf *h, const float *x, const float *xn, int64_t m, int niter, Buf<int32_t> &asg) {
+int lloyd(anr_ivf *h, const float *x, const float *xn, int64_t m, int niter, DevBuf<int32_t> &asg) {
   const int nl = h->nlist;
-  ANR_TRY(asg.need(m));
-  ANR_TRY(h->seg.need(2 * nl));
+  ANR_TRY(need(asg, m));
+  ANR_TRY(need(h->seg, 2 * nl));
   std::vector<int64_t> cnt, seg(2 * nl);
   for (int it = 0; it < niter; ++it) {
     ANR_TRY(assign_rows(h, x, xn, m, asg.p));
@@ -1179,9 +1147,9 @@ int lloyd(anr_ivf *h, const float *x, const float *xn, int64_t m, int niter, Buf
 }
 
 int alloc_centroids(anr_ivf *h) {
-  ANR_TRY(h->cent.need((int64_t)h->nlist * h->dim));
-  ANR_TRY(h->cn2.need(h->nlist));
-  ANR_TRY(h->cnrm.need(h->nlist));
+  ANR_TRY(need(h->cent, (int64_t)h->nlist * h->dim));
+  ANR_TRY(need(h->cn2, h->nlist));
+  ANR_TRY(need(h->cnrm, h->nlist));
   return ANR_OK;
 }
 
@@ -1196,12 +1164,12 @@ int search_impl(anr_ivf *h, const float *qin, bool host, int64_t nq, int k, int 
   h->last_exhaust = 0;
   if (nq == 0) return ANR_OK;
   ANR_TRY(ensure_built(h));
-  ANR_TRY(h->qbuf.need(nq * dim));
-  ANR_TRY(h->qnrm.need(nq));
+  ANR_TRY(need(h->qbuf, nq * dim));
+  ANR_TRY(need(h->qnrm, nq));
   ANR_TRY(stage_rows(h, qin, nq, host, h->qbuf.p, h->qnrm.p));
   // coarse
-  ANR_TRY(h->cs.need(nq * nl));
-  ANR_TRY(h->probe.need(nq * nprobe));
+  ANR_TRY(need(h->cs, nq * nl));
+  ANR_TRY(need(h->probe, nq * nprobe));
   hipLaunchKernelGGL(k_ivf_coarse, dim3((unsigned)nq, (unsigned)ceil_div(nl, 64)), dim3(256), 0, h->stream, h->qbuf.p, dim,
                      h->cent.p, nl, l2, h->cs.p);
   int np2 = 2;
@@ -1258,19 +1226,19 @@ int search_impl(anr_ivf *h, const float *qin, bool host, int64_t nq, int k, int 
   kp = std::min(kp, kSelCap);
   const bool trust16 = h->max_norm < 60000.0f;
 
-  ANR_TRY(h->cbase.need(nq));
-  ANR_TRY(h->ctot.need(nq));
-  ANR_TRY(h->qbound.need(nq));
-  ANR_TRY(h->ckey.need(std::max<int64_t>(total, 1)));
-  ANR_TRY(h->cpos.need(std::max<int64_t>(total, 1)));
-  ANR_TRY(h->eq.need(std::max<int64_t>(eq.size(), 1)));
-  ANR_TRY(h->eoff.need(std::max<int64_t>(eoff.size(), 1)));
-  ANR_TRY(h->items.need(std::max<int64_t>(items.size(), 1)));
-  ANR_TRY(h->qn2.need(nq));
-  ANR_TRY(h->Dd.need(nq * k));
-  ANR_TRY(h->Id.need(nq * k));
-  ANR_TRY(h->failq.need(nq));
-  ANR_TRY(h->qlist.need(nq));
+  ANR_TRY(need(h->cbase, nq));
+  ANR_TRY(need(h->ctot, nq));
+  ANR_TRY(need(h->qbound, nq));
+  ANR_TRY(need(h->ckey, std::max<int64_t>(total, 1)));
+  ANR_TRY(need(h->cpos, std::max<int64_t>(total, 1)));
+  ANR_TRY(need(h->eq, std::max<int64_t>(eq.size(), 1)));
+  ANR_TRY(need(h->eoff, std::max<int64_t>(eoff.size(), 1)));
+  ANR_TRY(need(h->items, std::max<int64_t>(items.size(), 1)));
+  ANR_TRY(need(h->qn2, nq));
+  ANR_TRY(need(h->Dd, nq * k));
+  ANR_TRY(need(h->Id, nq * k));
+  ANR_TRY(need(h->failq, nq));
+  ANR_TRY(need(h->qlist, nq));
   std::vector<float> qn2(nq);
   for (int64_t qi = 0; qi < nq; ++qi) qn2[qi] = (float)((double)qn[qi] * qn[qi]);
   ANR_HIP(hipMemcpyAsync(h->cbase.p, cbase.data(), nq * 8, hipMemcpyHostToDevice, h->stream));
@@ -1316,25 +1284,16 @@ int search_impl(anr_ivf *h, const float *qin, bool host, int64_t nq, int k, int 
 // product quantiser, host side
 
 template <typename T>
-int exact_alloc(Buf<T> &b, int64_t n) {  // persistent buffers of a PQ handle hold what they store, no growth slack
+int exact_alloc(DevBuf<T> &b, int64_t n) {  // persistent buffers of a PQ handle hold what they store, no growth slack
   if (b.cap != n) b.release();
-  return b.need(n);
+  return b.alloc(n, "ivf");
 }
 
 // device scratch of one encoding pass, released when the pass ends
 struct PqScratch {
-  Buf<float> x, xn, res, rn;
-  Buf<int32_t> asg, c32;
-  Buf<uint8_t> c8;
-  void release() {
-    x.release();
-    xn.release();
-    res.release();
-    rn.release();
-    asg.release();
-    c32.release();
-    c8.release();
-  }
+  DevBuf<float> x, xn, res, rn;
+  DevBuf<int32_t> asg, c32;
+  DevBuf<uint8_t> c8;
 };
 
 // |entry|^2 and |entry| of every codebook entry, and per sub-space the largest norm (the assignment's error bound)
@@ -1357,8 +1316,8 @@ int update_pq_stats(anr_ivf *h) {
 int pq_assign(anr_ivf *h, const float *res, const float *rn, int64_t n, int32_t *out) {
   if (n == 0) return ANR_OK;
   const int64_t nm = n * h->m;
-  ANR_TRY(h->fix.need(nm));
-  ANR_TRY(h->nfix.need(1));
+  ANR_TRY(need(h->fix, nm));
+  ANR_TRY(need(h->nfix, 1));
   ANR_HIP(hipMemsetAsync(h->nfix.p, 0, 4, h->stream));
   hipLaunchKernelGGL(k_pq_assign, dim3((unsigned)ceil_div(n, 64), (unsigned)h->m), dim3(256), 0, h->stream, res, n, h->dim,
                      h->dsub, h->m, h->cb.p, h->cbn2.p, rn, h->cbmax.p, out, h->fix.p, h->nfix.p);
@@ -1377,8 +1336,8 @@ int pq_assign(anr_ivf *h, const float *res, const float *rn, int64_t n, int32_t 
 // residuals of n preprocessed rows x (norms xn) against their coarse lists (written to asg) and the norms of their
 // sub-vectors, into sc.res / sc.rn
 int pq_residuals(anr_ivf *h, const float *x, const float *xn, int64_t n, int32_t *asg, PqScratch &sc) {
-  ANR_TRY(sc.res.need(n * h->dim));
-  ANR_TRY(sc.rn.need(n * h->m));
+  ANR_TRY(need(sc.res, n * h->dim));
+  ANR_TRY(need(sc.rn, n * h->m));
   ANR_TRY(assign_rows(h, x, xn, n, asg));
   hipLaunchKernelGGL(k_pq_residual, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, h->stream, x, n, h->dim, h->cent.p, asg,
                      sc.res.p);
@@ -1395,16 +1354,16 @@ int pq_residuals(anr_ivf *h, const float *x, const float *xn, int64_t n, int32_t
 int pq_lloyd(anr_ivf *h, const float *res, const float *rn, int64_t n, int niter) {
   const int64_t nm = n * h->m;
   const int nc = h->m * 256;
-  Buf<int32_t> asg;
-  Buf<int64_t> sg;
-  int r = asg.need(nm);
-  if (r == ANR_OK) r = sg.need(2 * nc);
-  if (r == ANR_OK) r = h->skeys.need(nm);
-  if (r == ANR_OK) r = h->skeys2.need(nm);
-  if (r == ANR_OK) r = h->svals.need(nm);
-  if (r == ANR_OK) r = h->svals2.need(nm);
-  if (r == ANR_OK) r = h->stemp.need((int64_t)radix_sort_temp_bytes(nm));
-  if (r == ANR_OK) r = h->counts.need(nc);
+  DevBuf<int32_t> asg;
+  DevBuf<int64_t> sg;
+  int r = need(asg, nm);
+  if (r == ANR_OK) r = need(sg, 2 * nc);
+  if (r == ANR_OK) r = need(h->skeys, nm);
+  if (r == ANR_OK) r = need(h->skeys2, nm);
+  if (r == ANR_OK) r = need(h->svals, nm);
+  if (r == ANR_OK) r = need(h->svals2, nm);
+  if (r == ANR_OK) r = need(h->stemp, (int64_t)radix_sort_temp_bytes(nm));
+  if (r == ANR_OK) r = need(h->counts, nc);
   std::vector<int32_t> cnt(nc);
   std::vector<int64_t> seg(2 * nc);
   for (int it = 0; it < niter && r == ANR_OK; ++it) {
@@ -1451,8 +1410,6 @@ int pq_lloyd(anr_ivf *h, const float *res, const float *rn, int64_t n, int niter
     if (hipGetLastError() != hipSuccess) r = fail(ANR_EHIP, "pq: launch failed");
     if (r == ANR_OK) r = update_pq_stats(h);
   }
-  asg.release();
-  sg.release();
   return r;
 }
 
@@ -1466,11 +1423,11 @@ int pq_encode(anr_ivf *h, const float *src, bool host, int64_t n, bool raw, floa
   std::vector<float> nr;
   for (int64_t s = 0; s < n && r == ANR_OK; s += kPqChunk) {
     const int64_t c = std::min<int64_t>(kPqChunk, n - s);
-    r = sc.x.need(c * dim);
-    if (r == ANR_OK) r = sc.xn.need(c);
-    if (r == ANR_OK) r = sc.asg.need(c);
-    if (r == ANR_OK) r = sc.c32.need(c * m);
-    if (r == ANR_OK) r = sc.c8.need(c * m);
+    r = need(sc.x, c * dim);
+    if (r == ANR_OK) r = need(sc.xn, c);
+    if (r == ANR_OK) r = need(sc.asg, c);
+    if (r == ANR_OK) r = need(sc.c32, c * m);
+    if (r == ANR_OK) r = need(sc.c8, c * m);
     if (r == ANR_OK) r = stage_rows(h, src + s * dim, c, host, sc.x.p, sc.xn.p, raw);
     if (r == ANR_OK) r = pq_residuals(h, sc.x.p, sc.xn.p, c, sc.asg.p, sc);
     if (r == ANR_OK) r = pq_assign(h, sc.res.p, sc.rn.p, c, sc.c32.p);
@@ -1491,7 +1448,6 @@ int pq_encode(anr_ivf *h, const float *src, bool host, int64_t n, bool raw, floa
     if (max_norm)
       for (float v : nr) *max_norm = std::max(*max_norm, v);
   }
-  sc.release();
   return r;
 }
 
@@ -1533,13 +1489,13 @@ int rebuild_pq(anr_ivf *h) {
   const int nl = h->nlist;
   h->list_cnt.assign(nl, 0);
   h->list_off.assign(nl + 1, 0);
-  Buf<int32_t> asg;
-  Buf<uint8_t> al, c8;
+  DevBuf<int32_t> asg;
+  DevBuf<uint8_t> al, c8;
   int r = ANR_OK;
   std::vector<int64_t> seg_start(nl);
   if (h->n_all > 0) {
-    r = asg.need(h->n_all);
-    if (r == ANR_OK) r = al.need(h->n_all);
+    r = need(asg, h->n_all);
+    if (r == ANR_OK) r = need(al, h->n_all);
     if (r == ANR_OK && (hipMemcpyAsync(asg.p, h->assign_h.data(), (size_t)h->n_all * 4, hipMemcpyHostToDevice,
                                        h->stream) != hipSuccess ||
                         hipMemcpyAsync(al.p, h->alive.data(), (size_t)h->n_all, hipMemcpyHostToDevice, h->stream) !=
@@ -1556,7 +1512,7 @@ int rebuild_pq(anr_ivf *h) {
   const int64_t npad = std::max<int64_t>(h->list_off[nl], kPqTile);
   if (r == ANR_OK) r = exact_alloc(h->lcodes, npad * h->m4);
   if (r == ANR_OK) r = exact_alloc(h->ids, npad);
-  if (r == ANR_OK) r = h->off_d.need(2 * nl);
+  if (r == ANR_OK) r = need(h->off_d, 2 * nl);
   if (r == ANR_OK && (hipMemsetAsync(h->lcodes.p, 0, (size_t)npad * h->m4 * 4, h->stream) != hipSuccess ||
                       hipMemsetAsync(h->ids.p, 0xff, (size_t)npad * 8, h->stream) != hipSuccess))
     r = fail(ANR_EHIP, "pq: memset failed");
@@ -1566,7 +1522,7 @@ int rebuild_pq(anr_ivf *h) {
       offs[l] = h->list_off[l];
       offs[nl + l] = seg_start[l];
     }
-    r = c8.need(h->n_all * h->m);
+    r = need(c8, h->n_all * h->m);
     if (r == ANR_OK &&
         (hipMemcpyAsync(c8.p, h->codes_h.data(), (size_t)h->n_all * h->m, hipMemcpyHostToDevice, h->stream) !=
              hipSuccess ||
@@ -1580,9 +1536,6 @@ int rebuild_pq(anr_ivf *h) {
     }
   }
   if (hipStreamSynchronize(h->stream) != hipSuccess && r == ANR_OK) r = fail(ANR_EHIP, "pq: rebuild failed");
-  asg.release();
-  al.release();
-  c8.release();
   for (auto *b : {&h->skeys, &h->skeys2}) b->release();
   for (auto *b : {&h->svals, &h->svals2}) b->release();
   h->stemp.release();
@@ -1602,11 +1555,11 @@ int search_pq(anr_ivf *h, const float *qin, bool host, int64_t nq, int k, int np
   h->last_exhaust = 0;
   if (nq == 0) return ANR_OK;
   ANR_TRY(ensure_built(h));
-  ANR_TRY(h->qbuf.need(nq * dim));
-  ANR_TRY(h->qnrm.need(nq));
+  ANR_TRY(need(h->qbuf, nq * dim));
+  ANR_TRY(need(h->qnrm, nq));
   ANR_TRY(stage_rows(h, qin, nq, host, h->qbuf.p, h->qnrm.p));
-  ANR_TRY(h->cs.need(nq * nl));
-  ANR_TRY(h->probe.need(nq * nprobe));
+  ANR_TRY(need(h->cs, nq * nl));
+  ANR_TRY(need(h->probe, nq * nprobe));
   hipLaunchKernelGGL(k_ivf_coarse, dim3((unsigned)nq, (unsigned)ceil_div(nl, 64)), dim3(256), 0, h->stream, h->qbuf.p, dim,
                      h->cent.p, nl, l2, h->cs.p);
   int np2 = 2;
@@ -1616,7 +1569,7 @@ int search_pq(anr_ivf *h, const float *qin, bool host, int64_t nq, int k, int np
   ANR_HIP(hipGetLastError());
   const int mp = 4 * h->m4;
   if (!l2) {  // the queries' inner-product LUTs, while the host waits for the probe lists
-    ANR_TRY(h->lut.need(nq * mp * 256));
+    ANR_TRY(need(h->lut, nq * mp * 256));
     hipLaunchKernelGGL(k_pq_lut, dim3((unsigned)nq, (unsigned)mp), dim3(256), 0, h->stream, h->qbuf.p, dim, h->dsub, h->m,
                        h->cb.p, h->lut.p);
     ANR_HIP(hipGetLastError());
@@ -1639,13 +1592,13 @@ int search_pq(anr_ivf *h, const float *qin, bool host, int64_t nq, int k, int np
     }
     total += ctot[qi];
   }
-  ANR_TRY(h->cbase.need(nq));
-  ANR_TRY(h->ctot.need(nq));
-  ANR_TRY(h->ckey.need(std::max<int64_t>(total, 1)));
-  ANR_TRY(h->cpos.need(std::max<int64_t>(total, 1)));
-  ANR_TRY(h->pitems.need(std::max<int64_t>(items.size(), 1)));
-  ANR_TRY(h->Dd.need(nq * k));
-  ANR_TRY(h->Id.need(nq * k));
+  ANR_TRY(need(h->cbase, nq));
+  ANR_TRY(need(h->ctot, nq));
+  ANR_TRY(need(h->ckey, std::max<int64_t>(total, 1)));
+  ANR_TRY(need(h->cpos, std::max<int64_t>(total, 1)));
+  ANR_TRY(need(h->pitems, std::max<int64_t>(items.size(), 1)));
+  ANR_TRY(need(h->Dd, nq * k));
+  ANR_TRY(need(h->Id, nq * k));
   ANR_HIP(hipMemcpyAsync(h->cbase.p, cbase.data(), nq * 8, hipMemcpyHostToDevice, h->stream));
   ANR_HIP(hipMemcpyAsync(h->ctot.p, ctot.data(), nq * 8, hipMemcpyHostToDevice, h->stream));
   if (!items.empty()) {
@@ -1680,9 +1633,9 @@ int train_pq(anr_ivf *h, const float *x_host, const std::vector<int64_t> &rows) 
   std::vector<float> xt((size_t)n * dim);
   for (int64_t i = 0; i < n; ++i) std::memcpy(&xt[i * dim], x_host + rows[i] * dim, (size_t)dim * 4);
   PqScratch sc;
-  int r = sc.x.need(n * dim);
-  if (r == ANR_OK) r = sc.xn.need(n);
-  if (r == ANR_OK) r = sc.asg.need(n);
+  int r = need(sc.x, n * dim);
+  if (r == ANR_OK) r = need(sc.xn, n);
+  if (r == ANR_OK) r = need(sc.asg, n);
   if (r == ANR_OK) r = stage_rows(h, xt.data(), n, true, sc.x.p, sc.xn.p);
   if (r == ANR_OK) r = pq_residuals(h, sc.x.p, sc.xn.p, n, sc.asg.p, sc);
   // codebook entry c of sub-space j = sub-vector j of residual row c: [c][j][dsub] -> [j][c][dsub]
@@ -1693,7 +1646,6 @@ int train_pq(anr_ivf *h, const float *x_host, const std::vector<int64_t> &rows) 
   if (r == ANR_OK) r = update_pq_stats(h);
   if (r == ANR_OK) r = pq_lloyd(h, sc.res.p, sc.rn.p, n, kPqNiter);
   if (r == ANR_OK) h->pq_ready = true;
-  sc.release();
   return r;
 }
 
@@ -1737,28 +1689,8 @@ int anr_ivf_create(int32_t dim, int32_t metric, int32_t normalize, int32_t nlist
 int anr_ivf_destroy(anr_ivf *h) {
   if (!h) return ANR_OK;
   DeviceGuard g(h->device);
-  for (auto *b : {&h->cent, &h->cn2, &h->cnrm, &h->xall, &h->xnrm, &h->xs, &h->ckey, &h->qbuf, &h->qnrm, &h->qn2,
-                  &h->qbound, &h->Dd})
-    b->release();
-  for (auto *b : {&h->assign, &h->counts, &h->fix, &h->nfix, &h->probe, &h->cpos, &h->failq, &h->qlist, &h->eq})
-    b->release();
-  for (auto *b : {&h->ids, &h->seg, &h->off_d, &h->cbase, &h->ctot, &h->eoff, &h->Id, &h->rid}) b->release();
-  h->rout.release();
-  for (auto *b : {&h->cb, &h->cbn2, &h->cbnrm, &h->cbmax, &h->lut}) b->release();
-  h->lcodes.release();
-  h->pitems.release();
-  h->alive_d.release();
-  h->x16.release();
-  h->n2.release();
-  h->cs.release();
-  h->skeys.release();
-  h->skeys2.release();
-  h->svals.release();
-  h->svals2.release();
-  h->stemp.release();
-  h->items.release();
   if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
+  delete h;  // frees every buffer of the handle, still under the guard
   return ANR_OK;
 }
 
@@ -1787,11 +1719,11 @@ int anr_ivf_train(anr_ivf *h, const float *x_host, int64_t n, int32_t niter, int
   std::vector<float> xt((size_t)m * dim), c0((size_t)h->nlist * dim);
   for (int64_t i = 0; i < m; ++i) std::memcpy(&xt[i * dim], x_host + sample[i] * dim, (size_t)dim * 4);
   for (int l = 0; l < h->nlist; ++l) std::memcpy(&c0[(size_t)l * dim], x_host + init[l] * dim, (size_t)dim * 4);
-  Buf<float> xd, xn, cn;
-  Buf<int32_t> asg;
-  int r = xd.need(m * dim);
-  if (r == ANR_OK) r = xn.need(m);
-  if (r == ANR_OK) r = cn.need(h->nlist);
+  DevBuf<float> xd, xn, cn;
+  DevBuf<int32_t> asg;
+  int r = need(xd, m * dim);
+  if (r == ANR_OK) r = need(xn, m);
+  if (r == ANR_OK) r = need(cn, h->nlist);
   if (r == ANR_OK) r = stage_rows(h, xt.data(), m, true, xd.p, xn.p);
   if (r == ANR_OK) r = stage_rows(h, c0.data(), h->nlist, true, h->cent.p, cn.p);
   if (r == ANR_OK) r = update_cstats(h);
@@ -1806,10 +1738,6 @@ int anr_ivf_train(anr_ivf *h, const float *x_host, int64_t n, int32_t niter, int
   }
   if (r == ANR_OK) r = reassign_all(h);
   if (r == ANR_OK && hipStreamSynchronize(h->stream) != hipSuccess) r = fail(ANR_EHIP, "train: stream failed");
-  xd.release();
-  xn.release();
-  cn.release();
-  asg.release();
   return r;
 }
 
@@ -1819,17 +1747,14 @@ int anr_ivf_train_from_centroids(anr_ivf *h, const float *x_host, int64_t n, int
   if (!h->trained) return fail(ANR_ESTATE, "anr_ivf_train_from_centroids: set the initial centroids first");
   DeviceGuard g(h->device);
   if (!g.ok) return fail(ANR_EHIP, "hipSetDevice(%d) failed", h->device);
-  Buf<float> xd, xn;
-  Buf<int32_t> asg;
-  int r = xd.need(n * h->dim);
-  if (r == ANR_OK) r = xn.need(n);
+  DevBuf<float> xd, xn;
+  DevBuf<int32_t> asg;
+  int r = need(xd, n * h->dim);
+  if (r == ANR_OK) r = need(xn, n);
   if (r == ANR_OK) r = stage_rows(h, x_host, n, true, xd.p, xn.p);
   if (r == ANR_OK) r = lloyd(h, xd.p, xn.p, n, niter, asg);
   if (r == ANR_OK) r = reassign_all(h);
   if (r == ANR_OK && hipStreamSynchronize(h->stream) != hipSuccess) r = fail(ANR_EHIP, "train: stream failed");
-  xd.release();
-  xn.release();
-  asg.release();
   return r;
 }
 
@@ -1955,8 +1880,8 @@ int anr_ivf_reconstruct(anr_ivf *h, const int64_t *ids, int64_t n, float *out_ho
       std::memcpy(out_host + i * h->dim, h->xh.data() + ids[i] * h->dim, (size_t)h->dim * 4);
     return ANR_OK;
   }
-  ANR_TRY(h->rid.need(n));
-  ANR_TRY(h->rout.need(n * h->dim));
+  ANR_TRY(need(h->rid, n));
+  ANR_TRY(need(h->rout, n * h->dim));
   ANR_HIP(hipMemcpyAsync(h->rid.p, ids, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(k_ivf_rows, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, h->stream, h->xall.p, h->dim, h->rid.p, n,
                      h->rout.p);
@@ -2003,10 +1928,10 @@ int anr_ivf_create_pq(int32_t dim, int32_t metric, int32_t normalize, int32_t nl
   h->m = m;
   h->m4 = (m + 3) / 4;
   h->dsub = dim / m;
-  int r = h->cb.need((int64_t)m * 256 * h->dsub);
-  if (r == ANR_OK) r = h->cbn2.need((int64_t)m * 256);
-  if (r == ANR_OK) r = h->cbnrm.need((int64_t)m * 256);
-  if (r == ANR_OK) r = h->cbmax.need(m);
+  int r = need(h->cb, (int64_t)m * 256 * h->dsub);
+  if (r == ANR_OK) r = need(h->cbn2, (int64_t)m * 256);
+  if (r == ANR_OK) r = need(h->cbnrm, (int64_t)m * 256);
+  if (r == ANR_OK) r = need(h->cbmax, m);
   if (r != ANR_OK) {
     anr_ivf_destroy(h);
     return r;
@@ -2048,13 +1973,13 @@ int anr_ivf_pq_train_from_codebooks(anr_ivf *h, const float *x_host, int64_t n, 
   DeviceGuard g(h->device);
   if (!g.ok) return fail(ANR_EHIP, "hipSetDevice(%d) failed", h->device);
   PqScratch sc;
-  int r = sc.x.need(n * h->dim);
-  if (r == ANR_OK) r = sc.xn.need(n);
-  if (r == ANR_OK) r = sc.asg.need(n);
+  int r = need(sc.x, n * h->dim);
+  if (r == ANR_OK) r = need(sc.xn, n);
+  if (r == ANR_OK) r = need(sc.asg, n);
   if (r == ANR_OK) r = stage_rows(h, x_host, n, true, sc.x.p, sc.xn.p);
   if (r == ANR_OK) r = pq_residuals(h, sc.x.p, sc.xn.p, n, sc.asg.p, sc);
   if (r == ANR_OK) r = pq_lloyd(h, sc.res.p, sc.rn.p, n, niter);
-  sc.release();
+  sc = PqScratch{};  // released before every row is encoded again
   if (r == ANR_OK) r = reencode_all(h);
   return r;
 }

@@ -4,7 +4,8 @@
 // host's random draws, Lloyd iterations with sklearn's two stopping rules, best of n_init.  Everything that decides
 // anything is float64 in one fixed order: distances |x|^2 + |c|^2 - 2 x.c with x.c (and both norms) from
 // v_mfma_f64_16x16x4_f64 in ascending k; sums over rows in fixed blocks (a 256-leaf tree per block, blocks in ascending
-// order); no floating-point atomics.  DESIGN.md §5j has the kernels, the orders and the byte counts;
+// order); no floating-point atomics.  gram_f64.hpp has the MFMA lane map, DESIGN.md §5j the kernels, the orders and the
+// byte counts;
 // tests/kmeans_ref.py restates the orders in numpy.  Compiled without multiply-add contraction (Makefile, EXACT).
 #include <algorithm>
 #include <climits>
@@ -13,23 +14,10 @@
 #include <vector>
 
 #include "common.hpp"
-#include "kmeans.hpp"
+#include "gram_f64.hpp"
+#include "graph.hpp"
 
 using namespace anr;
-
-// scratch kept on the index handle between calls, grown on demand
-struct anr_kmeans {
-  void *arena = nullptr;  // every array of one call
-  size_t arena_cap = 0;
-};
-
-namespace anr {
-void kmeans_free(anr_kmeans *q) {
-  if (!q) return;
-  if (q->arena) (void)hipFree(q->arena);
-  delete q;
-}
-}  // namespace anr
 
 namespace {
 
@@ -43,8 +31,6 @@ constexpr int kKmNT = 256;
 constexpr int kKmBlock = 256;    // leaves of a sum tree / elements of a scan block
 constexpr int kKmChunk = 512;    // rows of one update partial
 constexpr int kKmSlab = 128;     // dimensions of one update workgroup
-
-typedef double double4_t __attribute__((ext_vector_type(4)));
 
 // state the host reads once per Lloyd iteration
 struct KmCtrl {
@@ -93,11 +79,11 @@ struct KmDist {
   int first;              // 1: there is no closest distance yet
 };
 
-// Distances of 64 rows to all centres.  Wave w owns rows 16 w .. 16 w + 15 and every 16-centre block; operand lanes: A[i][k]
-// and B[k][j] sit in lane (i or j) + 16 k; result register r of block b is row 16 w + (lane >> 4) + 4 r, centre
-// 16 b + (lane & 15).  SEED = false: the nearest centre of every row, ties to the lower index (per lane over its blocks in
-// ascending order with <, then a xor butterfly over the 16 lanes of a row comparing (distance, index)), and the number of
-// rows whose label changed (an integer atomic).  SEED = true: min(closest, max(distance, 0)) per candidate.
+// Distances of 64 rows to all centres.  Wave w owns rows 16 w .. 16 w + 15 and every 16-centre block (the lane map of
+// gram_f64.hpp): result register r of block b is row 16 w + (lane >> 4) + 4 r, centre 16 b + (lane & 15).  SEED = false:
+// the nearest centre of every row, ties to the lower index (per lane over its blocks in ascending order with <, then a
+// xor butterfly over the 16 lanes of a row comparing (distance, index)), and the number of rows whose label changed (an
+// integer atomic).  SEED = true: min(closest, max(distance, 0)) per candidate.
 template <bool SEED>
 __global__ __launch_bounds__(kKmNT) void k_km_dist(KmDist p) {
   __shared__ float As[kKmTile][kKmLdA];
@@ -391,8 +377,6 @@ __global__ void k_km_rowinertia(const float *__restrict__ x32, int dim, int n, c
   v[i] = s;
 }
 
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // everything one call needs, carved from the handle's arena
 struct Plan {
   const float *x32;
@@ -486,38 +470,23 @@ extern "C" int anr_index_kmeans(anr_index *h, int32_t k, int32_t n_init, int32_t
   P.x32 = cur.x32, P.n = n, P.dim = dim, P.k = k, P.trials = n_local_trials, P.st = cur.stream;
   P.nb = (int)ceil_div(n, kKmBlock), P.nsb = (int)ceil_div(P.nb, kKmBlock), P.nchunks = (int)ceil_div(n, kKmChunk);
   const int tmax = std::max(1, (int)n_local_trials);
-  size_t at = 0;
-  auto take = [&](size_t bytes) {
-    const size_t r = at;
-    at = al256(at + bytes);
-    return r;
-  };
+  ArenaLayout<256> L;
   const size_t N = (size_t)n;
-  const size_t o_first = take((size_t)n_init * 4), o_u = take(n_u * 8), in_end = at;
-  const size_t o_ctrl = take(sizeof(KmCtrl)), o_nx = take(N * 8), o_closest = take(N * 8), o_local = take(N * 8);
-  const size_t o_candd = take(N * 8 * tmax), o_v = take(N * 8), o_btot = take((size_t)P.nb * 8), o_boff = take((size_t)P.nb * 8);
-  const size_t o_part = take((size_t)P.nb * 8 * tmax), o_part2 = take((size_t)P.nsb * 8 * tmax);
-  const size_t o_partial = take((size_t)P.nchunks * k * dim * 8), o_cnt = take((size_t)P.nchunks * k * 4);
-  const size_t o_c0 = take((size_t)k * dim * 8), o_c1 = take((size_t)k * dim * 8), o_cc = take((size_t)kKmMaxTrials * dim * 8);
-  const size_t o_cn = take(kKmMaxK * 8), o_mean = take((size_t)dim * 8), o_var = take((size_t)dim * 8);
-  const size_t o_l0 = take(N * 4), o_l1 = take(N * 4), o_cand = take(kKmMaxTrials * 4), o_ids = take(kKmMaxK * 4);
-  const size_t total = at;
+  const size_t o_first = L.take((size_t)n_init * 4), o_u = L.take(n_u * 8), in_end = L.at;
+  const size_t o_ctrl = L.take(sizeof(KmCtrl)), o_nx = L.take(N * 8), o_closest = L.take(N * 8), o_local = L.take(N * 8);
+  const size_t o_candd = L.take(N * 8 * tmax), o_v = L.take(N * 8), o_btot = L.take((size_t)P.nb * 8);
+  const size_t o_boff = L.take((size_t)P.nb * 8);
+  const size_t o_part = L.take((size_t)P.nb * 8 * tmax), o_part2 = L.take((size_t)P.nsb * 8 * tmax);
+  const size_t o_partial = L.take((size_t)P.nchunks * k * dim * 8), o_cnt = L.take((size_t)P.nchunks * k * 4);
+  const size_t o_c0 = L.take((size_t)k * dim * 8), o_c1 = L.take((size_t)k * dim * 8);
+  const size_t o_cc = L.take((size_t)kKmMaxTrials * dim * 8);
+  const size_t o_cn = L.take(kKmMaxK * 8), o_mean = L.take((size_t)dim * 8), o_var = L.take((size_t)dim * 8);
+  const size_t o_l0 = L.take(N * 4), o_l1 = L.take(N * 4), o_cand = L.take(kKmMaxTrials * 4), o_ids = L.take(kKmMaxK * 4);
+  const size_t total = L.at;
 
-  anr_kmeans *&q = index_kmeans(h);
-  if (!q) q = new anr_kmeans();
-  if (total > q->arena_cap) {
-    if (q->arena) (void)hipFree(q->arena);
-    q->arena = nullptr;
-    q->arena_cap = 0;
-    const size_t want = total + total / 4;
-    if (hipMalloc(&q->arena, want) != hipSuccess) {
-      q->arena = nullptr;
-      (void)hipGetLastError();
-      return fail(ANR_EHIP, "k-means: could not allocate %zu bytes of device memory", want);
-    }
-    q->arena_cap = want;
-  }
-  unsigned char *A = static_cast<unsigned char *>(q->arena);
+  DevBuf<unsigned char> &arena = index_scratch(h).km_arena;
+  ANR_TRY(arena.alloc((int64_t)total, "k-means", (int64_t)(total + total / 4)));
+  unsigned char *A = arena.p;
   auto D = [&](size_t o) { return reinterpret_cast<double *>(A + o); };
   auto I = [&](size_t o) { return reinterpret_cast<int *>(A + o); };
   P.first_rows = I(o_first), P.u = D(o_u), P.ctrl = reinterpret_cast<KmCtrl *>(A + o_ctrl), P.nx = D(o_nx);
@@ -573,7 +542,7 @@ extern "C" int anr_index_kmeans(anr_index *h, int32_t k, int32_t n_init, int32_t
       if (ctrl.empty) {
         if (stats) {
           std::fill(stats, stats + 8, (int64_t)0);
-          stats[0] = total_iters, stats[1] = assign_passes, stats[3] = (int64_t)q->arena_cap, stats[5] = init;
+          stats[0] = total_iters, stats[1] = assign_passes, stats[3] = arena.cap, stats[5] = init;
         }
         return fail(ANR_EEMPTY, "k-means: a cluster lost all its rows (init %d, iteration %d); sklearn relocates such a "
                                 "centre in an order that is not defined, so this input stays on sklearn", init, it);
@@ -626,7 +595,7 @@ extern "C" int anr_index_kmeans(anr_index *h, int32_t k, int32_t n_init, int32_t
     stats[0] = total_iters;
     stats[1] = assign_passes;
     stats[2] = (int64_t)n_init * k;
-    stats[3] = (int64_t)q->arena_cap;
+    stats[3] = arena.cap;
     stats[4] = ceil_div(dim, kKmKC) * (kKmKC / 4);
     stats[5] = -1;
     stats[6] = n_strict;

@@ -30,27 +30,21 @@ int sort_topk(const float *scores_dev, int64_t n, int k, bool larger_is_better, 
               int64_t *I_row, LargeKScratch *s, hipStream_t st) {
   if (n > 0x7fffffffLL) return fail(ANR_EINVAL, "top-k beyond 1024 supports at most 2^31-1 rows");
   if (s->n < n) {
-    (void)hipFree(s->iota); (void)hipFree(s->keys); (void)hipFree(s->rows); (void)hipFree(s->temp);
-    s->iota = s->rows = nullptr; s->keys = nullptr; s->temp = nullptr; s->n = 0; s->temp_bytes = 0;
-    ANR_HIP(hipMalloc(reinterpret_cast<void **>(&s->iota), (size_t)n * sizeof(unsigned)));
-    ANR_HIP(hipMalloc(reinterpret_cast<void **>(&s->rows), (size_t)n * sizeof(unsigned)));
-    ANR_HIP(hipMalloc(reinterpret_cast<void **>(&s->keys), (size_t)n * sizeof(float)));
-    hipLaunchKernelGGL(k_iota, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, s->iota, n);
-    const size_t bytes = radix_sort_temp_bytes(n);
-    ANR_HIP(hipMalloc(&s->temp, bytes));
-    s->temp_bytes = bytes;
+    free_largek(s);  // all four before the first allocation: the peak is one set, not two
+    ANR_TRY(s->iota.alloc(n, "top-k beyond 1024"));
+    ANR_TRY(s->rows.alloc(n, "top-k beyond 1024"));
+    ANR_TRY(s->keys.alloc(n, "top-k beyond 1024"));
+    hipLaunchKernelGGL(k_iota, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, s->iota.p, n);
+    ANR_TRY(s->temp.alloc((int64_t)radix_sort_temp_bytes(n), "top-k beyond 1024"));
     s->n = n;
   }
-  ANR_TRY(radix_sort_pairs_f32(s->temp, scores_dev, s->keys, s->iota, s->rows, n, larger_is_better, st));
-  hipLaunchKernelGGL(k_emit_sorted, dim3((unsigned)ceil_div(k, 256)), dim3(256), 0, st, s->keys, s->rows, n, k,
+  ANR_TRY(radix_sort_pairs_f32(s->temp.p, scores_dev, s->keys.p, s->iota.p, s->rows.p, n, larger_is_better, st));
+  hipLaunchKernelGGL(k_emit_sorted, dim3((unsigned)ceil_div(k, 256)), dim3(256), 0, st, s->keys.p, s->rows.p, n, k,
                      larger_is_better ? 1 : 0, id_offset, D_row, I_row);
   ANR_HIP(hipGetLastError());
   return ANR_OK;
 }
 
-void free_largek(LargeKScratch *s) {
-  (void)hipFree(s->iota); (void)hipFree(s->keys); (void)hipFree(s->rows); (void)hipFree(s->temp);
-  *s = LargeKScratch{};
-}
+void free_largek(LargeKScratch *s) { *s = LargeKScratch{}; }
 
 }  // namespace anr

@@ -471,10 +471,9 @@ using namespace anr;
 struct anr_notegraph {
   int device = 0;
   int64_t n = 0, E = 0, m = 0;  // m = 2E CSR entries
-  int64_t *rowptr = nullptr;
-  int32_t *nbr = nullptr;
-  double *wt = nullptr;
-  double *cent = nullptr, *imp = nullptr;
+  DevBuf<int64_t> rowptr;
+  DevBuf<int32_t> nbr;
+  DevBuf<double> wt, cent, imp;
   hipStream_t stream = nullptr;
   std::mutex mu;
   int64_t max_slots = 0;
@@ -482,67 +481,44 @@ struct anr_notegraph {
   int ws_slots = 0, ws_q = 0;
   bool ws_slots_limited = false, ws_q_limited = false;  // sized by free memory, not by the call that asked
   int64_t ws_cap = 0;
-  u64 *dist = nullptr;
-  int *stamp = nullptr, *touched = nullptr, *fa = nullptr, *fb = nullptr;
-  int *cnt_a = nullptr, *cnt_b = nullptr, *tcnt = nullptr;
-  NgSlot *slot = nullptr;
-  int *owner = nullptr, *res_id = nullptr, *res_pos = nullptr, *rcnt = nullptr;
-  double *res_dist = nullptr;
-  u64 *key_a = nullptr, *key_b = nullptr;
-  unsigned *val_a = nullptr, *val_b = nullptr;
-  double *score = nullptr;
-  void *sort_temp = nullptr;
-  int64_t *o_ids = nullptr;  // [ws_q][ws_cap] staging of the host outputs
-  double *o_dist = nullptr, *o_score = nullptr;
-  int32_t *o_pos = nullptr;
+  struct Workspace {
+    DevBuf<u64> dist;
+    DevBuf<int> stamp, touched, fa, fb, cnt_a, cnt_b, tcnt;
+    DevBuf<NgSlot> slot;
+    DevBuf<int> owner, res_id, res_pos, rcnt;
+    DevBuf<double> res_dist;
+    DevBuf<u64> key_a, key_b;
+    DevBuf<unsigned> val_a, val_b;
+    DevBuf<double> score;
+    DevBuf<unsigned char> sort_temp;
+    DevBuf<int64_t> o_ids;  // [ws_q][ws_cap] staging of the host outputs
+    DevBuf<double> o_dist, o_score;
+    DevBuf<int32_t> o_pos;
+  } ws;
   // graph quality workspace (components, hop histogram): its own buffers, grown when a call needs more, freed at destroy;
   // it shares nothing with the retrieve workspace above
   int64_t bfs_words = 0;      // ANR_NOTEGRAPH_OPT_BFS_WORDS, 0 = kNgBfsWords
-  int64_t q_state_cap = 0;    // u64 elements of q_state
-  u64 *q_state = nullptr;     // seen, frontier, next: 3 x [n][W]
-  int64_t q_src_cap = 0;
-  int32_t *q_src = nullptr;   // the explicit sources of a call
-  int32_t *q_label = nullptr;  // [n]
-  u64 *q_cnt = nullptr;       // [2] level counters, [2] root count
-  int *q_flag = nullptr;
+  DevBuf<u64> q_state;        // seen, frontier, next: 3 x [n][W]
+  DevBuf<int32_t> q_src;      // the explicit sources of a call
+  DevBuf<int32_t> q_label;    // [n]
+  DevBuf<u64> q_cnt;          // [2] level counters, [2] root count
+  DevBuf<int> q_flag;
 };
 
 namespace {
 
-template <typename T>
-int g_alloc(T **p, int64_t n) {
-  *p = nullptr;
-  ANR_HIP(hipMalloc(reinterpret_cast<void **>(p), (size_t)(n > 0 ? n : 1) * sizeof(T)));
-  return ANR_OK;
-}
-template <typename T>
-void g_free(T *&p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
-
 inline unsigned blocks(int64_t n, int per = 256) { return (unsigned)std::max<int64_t>(1, ceil_div(n, per)); }
 
 void free_workspace(anr_notegraph *h) {
-  g_free(h->dist); g_free(h->stamp); g_free(h->touched); g_free(h->fa); g_free(h->fb);
-  g_free(h->cnt_a); g_free(h->cnt_b); g_free(h->tcnt); g_free(h->slot);
-  g_free(h->owner); g_free(h->res_id); g_free(h->res_pos); g_free(h->rcnt); g_free(h->res_dist);
-  g_free(h->key_a); g_free(h->key_b); g_free(h->val_a); g_free(h->val_b); g_free(h->score);
-  g_free(h->sort_temp);
-  g_free(h->o_ids); g_free(h->o_dist); g_free(h->o_score); g_free(h->o_pos);
+  h->ws = anr_notegraph::Workspace{};
   h->ws_slots = h->ws_q = 0;
   h->ws_cap = 0;
   h->ws_slots_limited = h->ws_q_limited = false;
 }
 
-void free_quality_workspace(anr_notegraph *h) {
-  g_free(h->q_state); g_free(h->q_src); g_free(h->q_label); g_free(h->q_cnt); g_free(h->q_flag);
-  h->q_state_cap = h->q_src_cap = 0;
-}
-
 int ensure_quality_small(anr_notegraph *h) {
-  if (!h->q_cnt) ANR_TRY(g_alloc(&h->q_cnt, 4));
-  if (!h->q_flag) ANR_TRY(g_alloc(&h->q_flag, 1));
+  ANR_TRY(h->q_cnt.alloc(4, "note graph"));
+  ANR_TRY(h->q_flag.alloc(1, "note graph"));
   return ANR_OK;
 }
 
@@ -561,7 +537,7 @@ int ensure_workspace(anr_notegraph *h, int64_t want_slots, int64_t want_q, int64
     want_q = std::min(want_q, h->max_slots);
   }
   const int64_t ocap = host_out ? cap : 0;
-  if (h->dist && (h->ws_slots >= want_slots || h->ws_slots_limited) && (h->ws_q >= want_q || h->ws_q_limited) &&
+  if (h->ws.dist.p && (h->ws_slots >= want_slots || h->ws_slots_limited) && (h->ws_q >= want_q || h->ws_q_limited) &&
       h->ws_cap >= ocap)
     return ANR_OK;
   // the held workspace is too small (or of another shape): sized anew from the memory that is free without it
@@ -577,36 +553,36 @@ int ensure_workspace(anr_notegraph *h, int64_t want_slots, int64_t want_q, int64
   const int64_t ns_b = std::min(want_slots, std::max<int64_t>(1, (budget - nq_b * query_bytes(n, ocap)) / slot_bytes(n)));
   h->ws_q_limited = nq_b < want_q && !(h->max_slots > 0 && nq_b == h->max_slots);
   h->ws_slots_limited = ns_b < want_slots;
-  ANR_TRY(g_alloc(&h->dist, ns_b * n));
-  ANR_TRY(g_alloc(&h->stamp, ns_b * n));
-  ANR_TRY(g_alloc(&h->touched, ns_b * n));
-  ANR_TRY(g_alloc(&h->fa, ns_b * n));
-  ANR_TRY(g_alloc(&h->fb, ns_b * n));
-  ANR_TRY(g_alloc(&h->cnt_a, ns_b));
-  ANR_TRY(g_alloc(&h->cnt_b, ns_b));
-  ANR_TRY(g_alloc(&h->tcnt, ns_b));
-  ANR_TRY(g_alloc(&h->slot, ns_b));
-  ANR_TRY(g_alloc(&h->owner, nq_b * n));
-  ANR_TRY(g_alloc(&h->res_id, nq_b * n));
-  ANR_TRY(g_alloc(&h->res_pos, nq_b * n));
-  ANR_TRY(g_alloc(&h->res_dist, nq_b * n));
-  ANR_TRY(g_alloc(&h->rcnt, nq_b));
-  ANR_TRY(g_alloc(&h->key_a, n));
-  ANR_TRY(g_alloc(&h->key_b, n));
-  ANR_TRY(g_alloc(&h->val_a, n));
-  ANR_TRY(g_alloc(&h->val_b, n));
-  ANR_TRY(g_alloc(&h->score, n));
-  ANR_HIP(hipMalloc(&h->sort_temp, radix_sort_temp_bytes(n)));
+  ANR_TRY(h->ws.dist.alloc(ns_b * n, "note graph"));
+  ANR_TRY(h->ws.stamp.alloc(ns_b * n, "note graph"));
+  ANR_TRY(h->ws.touched.alloc(ns_b * n, "note graph"));
+  ANR_TRY(h->ws.fa.alloc(ns_b * n, "note graph"));
+  ANR_TRY(h->ws.fb.alloc(ns_b * n, "note graph"));
+  ANR_TRY(h->ws.cnt_a.alloc(ns_b, "note graph"));
+  ANR_TRY(h->ws.cnt_b.alloc(ns_b, "note graph"));
+  ANR_TRY(h->ws.tcnt.alloc(ns_b, "note graph"));
+  ANR_TRY(h->ws.slot.alloc(ns_b, "note graph"));
+  ANR_TRY(h->ws.owner.alloc(nq_b * n, "note graph"));
+  ANR_TRY(h->ws.res_id.alloc(nq_b * n, "note graph"));
+  ANR_TRY(h->ws.res_pos.alloc(nq_b * n, "note graph"));
+  ANR_TRY(h->ws.res_dist.alloc(nq_b * n, "note graph"));
+  ANR_TRY(h->ws.rcnt.alloc(nq_b, "note graph"));
+  ANR_TRY(h->ws.key_a.alloc(n, "note graph"));
+  ANR_TRY(h->ws.key_b.alloc(n, "note graph"));
+  ANR_TRY(h->ws.val_a.alloc(n, "note graph"));
+  ANR_TRY(h->ws.val_b.alloc(n, "note graph"));
+  ANR_TRY(h->ws.score.alloc(n, "note graph"));
+  ANR_TRY(h->ws.sort_temp.alloc((int64_t)radix_sort_temp_bytes(n), "note graph"));
   if (ocap > 0) {
-    ANR_TRY(g_alloc(&h->o_ids, nq_b * ocap));
-    ANR_TRY(g_alloc(&h->o_dist, nq_b * ocap));
-    ANR_TRY(g_alloc(&h->o_score, nq_b * ocap));
-    ANR_TRY(g_alloc(&h->o_pos, nq_b * ocap));
+    ANR_TRY(h->ws.o_ids.alloc(nq_b * ocap, "note graph"));
+    ANR_TRY(h->ws.o_dist.alloc(nq_b * ocap, "note graph"));
+    ANR_TRY(h->ws.o_score.alloc(nq_b * ocap, "note graph"));
+    ANR_TRY(h->ws.o_pos.alloc(nq_b * ocap, "note graph"));
   }
   // the one n-wide fill of a slot's life: when it is allocated
-  hipLaunchKernelGGL(k_ng_fill_u64, dim3(blocks(ns_b * n)), dim3(256), 0, h->stream, h->dist, ns_b * n, kNgInf);
-  hipLaunchKernelGGL(k_ng_fill_i32, dim3(blocks(ns_b * n)), dim3(256), 0, h->stream, h->stamp, ns_b * n, 0);
-  hipLaunchKernelGGL(k_ng_fill_i32, dim3(blocks(nq_b * n)), dim3(256), 0, h->stream, h->owner, nq_b * n, 0x7fffffff);
+  hipLaunchKernelGGL(k_ng_fill_u64, dim3(blocks(ns_b * n)), dim3(256), 0, h->stream, h->ws.dist.p, ns_b * n, kNgInf);
+  hipLaunchKernelGGL(k_ng_fill_i32, dim3(blocks(ns_b * n)), dim3(256), 0, h->stream, h->ws.stamp.p, ns_b * n, 0);
+  hipLaunchKernelGGL(k_ng_fill_i32, dim3(blocks(nq_b * n)), dim3(256), 0, h->stream, h->ws.owner.p, nq_b * n, 0x7fffffff);
   ANR_HIP(hipGetLastError());
   h->ws_slots = (int)ns_b;
   h->ws_q = (int)nq_b;
@@ -614,16 +590,17 @@ int ensure_workspace(anr_notegraph *h, int64_t want_slots, int64_t want_q, int64
   return ANR_OK;
 }
 
-// the searches of `ns` slots (already in h->slot) to their fixed point, merged into their queries' result lists
+// the searches of `ns` slots (already in h->ws.slot) to their fixed point, merged into their queries' result lists
 int run_slots(anr_notegraph *h, const std::vector<NgSlot> &slots, int64_t s0, int ns, double cutoff) {
   hipStream_t st = h->stream;
-  ANR_HIP(hipMemcpyAsync(h->slot, slots.data() + s0, (size_t)ns * sizeof(NgSlot), hipMemcpyHostToDevice, st));
+  const anr_notegraph::Workspace &ws = h->ws;
+  ANR_HIP(hipMemcpyAsync(ws.slot.p, slots.data() + s0, (size_t)ns * sizeof(NgSlot), hipMemcpyHostToDevice, st));
   NgSearch p{};
-  p.rowptr = h->rowptr; p.nbr = h->nbr; p.wt = h->wt; p.n = h->n; p.cutoff = cutoff;
-  p.dist = h->dist; p.stamp = h->stamp; p.touched = h->touched;
-  p.fin = h->fa; p.fout = h->fb; p.cnt_in = h->cnt_a; p.cnt_out = h->cnt_b; p.tcnt = h->tcnt;
-  p.slot = h->slot; p.nslots = ns; p.round = 0;
-  p.owner = h->owner; p.res_id = h->res_id; p.res_pos = h->res_pos; p.res_dist = h->res_dist; p.rcnt = h->rcnt;
+  p.rowptr = h->rowptr.p; p.nbr = h->nbr.p; p.wt = h->wt.p; p.n = h->n; p.cutoff = cutoff;
+  p.dist = ws.dist.p; p.stamp = ws.stamp.p; p.touched = ws.touched.p;
+  p.fin = ws.fa.p; p.fout = ws.fb.p; p.cnt_in = ws.cnt_a.p; p.cnt_out = ws.cnt_b.p; p.tcnt = ws.tcnt.p;
+  p.slot = ws.slot.p; p.nslots = ns; p.round = 0;
+  p.owner = ws.owner.p; p.res_id = ws.res_id.p; p.res_pos = ws.res_pos.p; p.res_dist = ws.res_dist.p; p.rcnt = ws.rcnt.p;
   hipLaunchKernelGGL(k_ng_seed, dim3(blocks(ns)), dim3(256), 0, st, p);
   std::vector<int> cnt((size_t)ns);
   int64_t maxc = 1;
@@ -671,6 +648,7 @@ int retrieve_impl(anr_notegraph *h, int64_t nq, const int64_t *seed_offs, const 
   if (nq == 0) return ANR_OK;
   const int64_t n = h->n;
   hipStream_t st = h->stream;
+  const anr_notegraph::Workspace &ws = h->ws;  // sized below; the buffers themselves do not move
   // the busiest batch this call could form: every query, every valid seed
   int64_t valid = 0;
   for (int64_t e = 0; e < seed_offs[nq]; ++e) valid += (seeds[e] >= 0 && seeds[e] < n);
@@ -684,40 +662,40 @@ int retrieve_impl(anr_notegraph *h, int64_t nq, const int64_t *seed_offs, const 
       for (int64_t e = seed_offs[q0 + ql]; e < seed_offs[q0 + ql + 1]; ++e)
         if (seeds[e] >= 0 && seeds[e] < n)
           slots.push_back(NgSlot{(int32_t)seeds[e], (int32_t)(e - seed_offs[q0 + ql]), ql});
-    ANR_HIP(hipMemsetAsync(h->rcnt, 0, (size_t)nqb * sizeof(int), st));
+    ANR_HIP(hipMemsetAsync(ws.rcnt.p, 0, (size_t)nqb * sizeof(int), st));
     // slots in (query, seed position) order: an earlier sub-batch holds the earlier seeds of a query, so the owner row
     // it leaves behind already belongs to them
     for (int64_t s0 = 0; s0 < (int64_t)slots.size(); s0 += h->ws_slots)
       ANR_TRY(run_slots(h, slots, s0, (int)std::min<int64_t>(h->ws_slots, (int64_t)slots.size() - s0), cutoff));
     found.assign((size_t)nqb, 0);
-    ANR_HIP(hipMemcpyAsync(found.data(), h->rcnt, (size_t)nqb * sizeof(int), hipMemcpyDeviceToHost, st));
+    ANR_HIP(hipMemcpyAsync(found.data(), ws.rcnt.p, (size_t)nqb * sizeof(int), hipMemcpyDeviceToHost, st));
     ANR_HIP(hipStreamSynchronize(st));
     for (int ql = 0; ql < nqb; ++ql) {
       const int64_t f = found[ql], m = std::min<int64_t>(f, cap), q = q0 + ql;
       NgOrder o{};
-      o.res_id = h->res_id + (int64_t)ql * n; o.res_pos = h->res_pos + (int64_t)ql * n;
-      o.res_dist = h->res_dist + (int64_t)ql * n; o.cent = h->cent; o.imp = h->imp; o.score = h->score;
-      o.owner = h->owner + (int64_t)ql * n; o.f = f;
-      const unsigned *perm = h->val_a;
+      o.res_id = ws.res_id.p + (int64_t)ql * n; o.res_pos = ws.res_pos.p + (int64_t)ql * n;
+      o.res_dist = ws.res_dist.p + (int64_t)ql * n; o.cent = h->cent.p; o.imp = h->imp.p; o.score = ws.score.p;
+      o.owner = ws.owner.p + (int64_t)ql * n; o.f = f;
+      const unsigned *perm = ws.val_a.p;
       if (f > 0) {
         // four stable passes, least significant key first: id, dist, seed position, score (descending)
-        hipLaunchKernelGGL(k_ng_score, dim3(blocks(f)), dim3(256), 0, st, o, h->key_a, h->val_a);
-        ANR_TRY(radix_sort_pairs_u64(h->sort_temp, h->key_a, h->key_b, h->val_a, h->val_b, f, false, st));
-        hipLaunchKernelGGL(k_ng_keys, dim3(blocks(f)), dim3(256), 0, st, o, h->val_b, f, 0, h->key_a);
-        ANR_TRY(radix_sort_pairs_u64(h->sort_temp, h->key_a, h->key_b, h->val_b, h->val_a, f, false, st));
-        hipLaunchKernelGGL(k_ng_keys, dim3(blocks(f)), dim3(256), 0, st, o, h->val_a, f, 1, h->key_a);
-        ANR_TRY(radix_sort_pairs_u64(h->sort_temp, h->key_a, h->key_b, h->val_a, h->val_b, f, false, st));
-        hipLaunchKernelGGL(k_ng_keys, dim3(blocks(f)), dim3(256), 0, st, o, h->val_b, f, 2, h->key_a);
-        ANR_TRY(radix_sort_pairs_u64(h->sort_temp, h->key_a, h->key_b, h->val_b, h->val_a, f, true, st));
+        hipLaunchKernelGGL(k_ng_score, dim3(blocks(f)), dim3(256), 0, st, o, ws.key_a.p, ws.val_a.p);
+        ANR_TRY(radix_sort_pairs_u64(ws.sort_temp.p, ws.key_a.p, ws.key_b.p, ws.val_a.p, ws.val_b.p, f, false, st));
+        hipLaunchKernelGGL(k_ng_keys, dim3(blocks(f)), dim3(256), 0, st, o, ws.val_b.p, f, 0, ws.key_a.p);
+        ANR_TRY(radix_sort_pairs_u64(ws.sort_temp.p, ws.key_a.p, ws.key_b.p, ws.val_b.p, ws.val_a.p, f, false, st));
+        hipLaunchKernelGGL(k_ng_keys, dim3(blocks(f)), dim3(256), 0, st, o, ws.val_a.p, f, 1, ws.key_a.p);
+        ANR_TRY(radix_sort_pairs_u64(ws.sort_temp.p, ws.key_a.p, ws.key_b.p, ws.val_a.p, ws.val_b.p, f, false, st));
+        hipLaunchKernelGGL(k_ng_keys, dim3(blocks(f)), dim3(256), 0, st, o, ws.val_b.p, f, 2, ws.key_a.p);
+        ANR_TRY(radix_sort_pairs_u64(ws.sort_temp.p, ws.key_a.p, ws.key_b.p, ws.val_b.p, ws.val_a.p, f, true, st));
         if (!host_out) {  // the best m again, by id
-          hipLaunchKernelGGL(k_ng_keys, dim3(blocks(m)), dim3(256), 0, st, o, h->val_a, m, 3, h->key_a);
-          ANR_TRY(radix_sort_pairs_u64(h->sort_temp, h->key_a, h->key_b, h->val_a, h->val_b, m, false, st));
-          perm = h->val_b;
+          hipLaunchKernelGGL(k_ng_keys, dim3(blocks(m)), dim3(256), 0, st, o, ws.val_a.p, m, 3, ws.key_a.p);
+          ANR_TRY(radix_sort_pairs_u64(ws.sort_temp.p, ws.key_a.p, ws.key_b.p, ws.val_a.p, ws.val_b.p, m, false, st));
+          perm = ws.val_b.p;
         }
       }
       if (host_out) {
-        hipLaunchKernelGGL(k_ng_out_host, dim3(blocks(cap)), dim3(256), 0, st, o, perm, m, cap, h->o_ids + (int64_t)ql * cap,
-                           h->o_dist + (int64_t)ql * cap, h->o_score + (int64_t)ql * cap, h->o_pos + (int64_t)ql * cap);
+        hipLaunchKernelGGL(k_ng_out_host, dim3(blocks(cap)), dim3(256), 0, st, o, perm, m, cap, ws.o_ids.p + (int64_t)ql * cap,
+                           ws.o_dist.p + (int64_t)ql * cap, ws.o_score.p + (int64_t)ql * cap, ws.o_pos.p + (int64_t)ql * cap);
         out_count[q] = (int32_t)f;
       } else {
         hipLaunchKernelGGL(k_ng_out_dev, dim3(blocks(cap)), dim3(256), 0, st, o, perm, m, cap, ids_dev + q * cap,
@@ -728,10 +706,10 @@ int retrieve_impl(anr_notegraph *h, int64_t nq, const int64_t *seed_offs, const 
     ANR_HIP(hipGetLastError());
     if (host_out) {
       const size_t cnt = (size_t)nqb * (size_t)cap;
-      ANR_HIP(hipMemcpyAsync(out_ids + q0 * cap, h->o_ids, cnt * 8, hipMemcpyDeviceToHost, st));
-      if (out_dist) ANR_HIP(hipMemcpyAsync(out_dist + q0 * cap, h->o_dist, cnt * 8, hipMemcpyDeviceToHost, st));
-      if (out_score) ANR_HIP(hipMemcpyAsync(out_score + q0 * cap, h->o_score, cnt * 8, hipMemcpyDeviceToHost, st));
-      if (out_pos) ANR_HIP(hipMemcpyAsync(out_pos + q0 * cap, h->o_pos, cnt * 4, hipMemcpyDeviceToHost, st));
+      ANR_HIP(hipMemcpyAsync(out_ids + q0 * cap, ws.o_ids.p, cnt * 8, hipMemcpyDeviceToHost, st));
+      if (out_dist) ANR_HIP(hipMemcpyAsync(out_dist + q0 * cap, ws.o_dist.p, cnt * 8, hipMemcpyDeviceToHost, st));
+      if (out_score) ANR_HIP(hipMemcpyAsync(out_score + q0 * cap, ws.o_score.p, cnt * 8, hipMemcpyDeviceToHost, st));
+      if (out_pos) ANR_HIP(hipMemcpyAsync(out_pos + q0 * cap, ws.o_pos.p, cnt * 4, hipMemcpyDeviceToHost, st));
     }
     ANR_HIP(hipStreamSynchronize(st));
   }
@@ -766,50 +744,48 @@ int anr_notegraph_create(int32_t device, int64_t n_nodes, int64_t n_edges, const
   h->E = n_edges;
   h->m = 2 * n_edges;
   const int64_t E = n_edges, m = h->m, n = n_nodes;
-  int64_t *d_src = nullptr, *d_dst = nullptr;
-  double *d_w = nullptr;
-  u64 *k0 = nullptr, *k1 = nullptr;
-  unsigned *v0 = nullptr, *v1 = nullptr;
-  void *temp = nullptr;
-  int *d_dup = nullptr;
   int dup = 0;
-  auto body = [&]() -> int {
+  auto body = [&]() -> int {  // a failure destroys the handle below
+    DevBuf<int64_t> d_src, d_dst;  // the build's buffers, of this call only
+    DevBuf<double> d_w;
+    DevBuf<u64> k0, k1;
+    DevBuf<unsigned> v0, v1;
+    DevBuf<unsigned char> temp;
+    DevBuf<int> d_dup;
     ANR_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     hipStream_t st = h->stream;
-    ANR_TRY(g_alloc(&h->rowptr, n + 1));
-    ANR_TRY(g_alloc(&h->nbr, m));
-    ANR_TRY(g_alloc(&h->wt, m));
-    ANR_TRY(g_alloc(&h->cent, n));
-    ANR_TRY(g_alloc(&h->imp, n));
-    ANR_HIP(hipMemsetAsync(h->cent, 0, (size_t)n * 8, st));
-    hipLaunchKernelGGL(k_ng_fill_f64, dim3(blocks(n)), dim3(256), 0, st, h->imp, n, 1.0);
-    ANR_TRY(g_alloc(&d_dup, 1));
-    ANR_HIP(hipMemsetAsync(d_dup, 0, sizeof(int), st));
+    ANR_TRY(h->rowptr.alloc(n + 1, "note graph"));
+    ANR_TRY(h->nbr.alloc(m, "note graph"));
+    ANR_TRY(h->wt.alloc(m, "note graph"));
+    ANR_TRY(h->cent.alloc(n, "note graph"));
+    ANR_TRY(h->imp.alloc(n, "note graph"));
+    ANR_HIP(hipMemsetAsync(h->cent.p, 0, (size_t)n * 8, st));
+    hipLaunchKernelGGL(k_ng_fill_f64, dim3(blocks(n)), dim3(256), 0, st, h->imp.p, n, 1.0);
+    ANR_TRY(d_dup.alloc(1, "note graph"));
+    ANR_HIP(hipMemsetAsync(d_dup.p, 0, sizeof(int), st));
     if (E > 0) {
-      ANR_TRY(g_alloc(&d_src, E));
-      ANR_TRY(g_alloc(&d_dst, E));
-      ANR_TRY(g_alloc(&d_w, E));
-      ANR_TRY(g_alloc(&k0, m));
-      ANR_TRY(g_alloc(&k1, m));
-      ANR_TRY(g_alloc(&v0, m));
-      ANR_TRY(g_alloc(&v1, m));
-      ANR_HIP(hipMalloc(&temp, radix_sort_temp_bytes(m)));
-      ANR_HIP(hipMemcpyAsync(d_src, src, (size_t)E * 8, hipMemcpyHostToDevice, st));
-      ANR_HIP(hipMemcpyAsync(d_dst, dst, (size_t)E * 8, hipMemcpyHostToDevice, st));
-      ANR_HIP(hipMemcpyAsync(d_w, w, (size_t)E * 8, hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(k_ng_edge_keys, dim3(blocks(m)), dim3(256), 0, st, d_src, d_dst, E, k0, v0);
-      ANR_TRY(radix_sort_pairs_u64(temp, k0, k1, v0, v1, m, false, st));
-      hipLaunchKernelGGL(k_ng_csr_fill, dim3(blocks(m)), dim3(256), 0, st, k1, v1, d_w, E, h->nbr, h->wt, d_dup);
+      ANR_TRY(d_src.alloc(E, "note graph"));
+      ANR_TRY(d_dst.alloc(E, "note graph"));
+      ANR_TRY(d_w.alloc(E, "note graph"));
+      ANR_TRY(k0.alloc(m, "note graph"));
+      ANR_TRY(k1.alloc(m, "note graph"));
+      ANR_TRY(v0.alloc(m, "note graph"));
+      ANR_TRY(v1.alloc(m, "note graph"));
+      ANR_TRY(temp.alloc((int64_t)radix_sort_temp_bytes(m), "note graph"));
+      ANR_HIP(hipMemcpyAsync(d_src.p, src, (size_t)E * 8, hipMemcpyHostToDevice, st));
+      ANR_HIP(hipMemcpyAsync(d_dst.p, dst, (size_t)E * 8, hipMemcpyHostToDevice, st));
+      ANR_HIP(hipMemcpyAsync(d_w.p, w, (size_t)E * 8, hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL(k_ng_edge_keys, dim3(blocks(m)), dim3(256), 0, st, d_src.p, d_dst.p, E, k0.p, v0.p);
+      ANR_TRY(radix_sort_pairs_u64(temp.p, k0.p, k1.p, v0.p, v1.p, m, false, st));
+      hipLaunchKernelGGL(k_ng_csr_fill, dim3(blocks(m)), dim3(256), 0, st, k1.p, v1.p, d_w.p, E, h->nbr.p, h->wt.p, d_dup.p);
     }
-    hipLaunchKernelGGL(k_ng_rowptr, dim3(blocks(n + 1)), dim3(256), 0, st, k1, m, n, h->rowptr);
+    hipLaunchKernelGGL(k_ng_rowptr, dim3(blocks(n + 1)), dim3(256), 0, st, k1.p, m, n, h->rowptr.p);
     ANR_HIP(hipGetLastError());
-    ANR_HIP(hipMemcpyAsync(&dup, d_dup, sizeof(int), hipMemcpyDeviceToHost, st));
+    ANR_HIP(hipMemcpyAsync(&dup, d_dup.p, sizeof(int), hipMemcpyDeviceToHost, st));
     ANR_HIP(hipStreamSynchronize(st));
     return ANR_OK;
   };
   int rc = body();
-  g_free(d_src); g_free(d_dst); g_free(d_w); g_free(k0); g_free(k1); g_free(v0); g_free(v1); g_free(d_dup);
-  if (temp) (void)hipFree(temp);
   if (rc == ANR_OK && dup) rc = fail(ANR_EINVAL, "an undirected pair is given more than once");
   if (rc != ANR_OK) {
     anr_notegraph_destroy(h);
@@ -823,11 +799,8 @@ int anr_notegraph_destroy(anr_notegraph *h) {
   if (!h) return ANR_OK;
   DeviceGuard g(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  free_workspace(h);
-  free_quality_workspace(h);
-  g_free(h->rowptr); g_free(h->nbr); g_free(h->wt); g_free(h->cent); g_free(h->imp);
   if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
+  delete h;  // frees the graph and both workspaces, still under the guard
   return ANR_OK;
 }
 
@@ -838,24 +811,25 @@ int anr_notegraph_pagerank(anr_notegraph *h, double alpha, int32_t max_iter, dou
   DeviceGuard g(h->device);
   hipStream_t st = h->stream;
   const int64_t n = h->n, m = h->m, nb = ceil_div(n, kNgChunk);
-  double *inv = nullptr, *a = nullptr, *x = nullptr, *xn = nullptr, *part = nullptr, *scal = nullptr;
   int done = 0;
   bool converged = false;
-  auto body = [&]() -> int {
-    ANR_TRY(g_alloc(&inv, n));
-    ANR_TRY(g_alloc(&a, m));
-    ANR_TRY(g_alloc(&x, n));
-    ANR_TRY(g_alloc(&xn, n));
-    ANR_TRY(g_alloc(&part, 2 * nb));
-    ANR_TRY(g_alloc(&scal, 2));
+  auto body = [&]() -> int {  // *iters is set below whatever comes of it
+    DevBuf<double> b_inv, b_a, b_x, b_xn, b_part, b_scal;  // of this call
+    ANR_TRY(b_inv.alloc(n, "note graph"));
+    ANR_TRY(b_a.alloc(m, "note graph"));
+    ANR_TRY(b_x.alloc(n, "note graph"));
+    ANR_TRY(b_xn.alloc(n, "note graph"));
+    ANR_TRY(b_part.alloc(2 * nb, "note graph"));
+    ANR_TRY(b_scal.alloc(2, "note graph"));
+    double *inv = b_inv.p, *a = b_a.p, *x = b_x.p, *xn = b_xn.p, *part = b_part.p, *scal = b_scal.p;  // x and xn swap
     const double p = 1.0 / (double)n;
-    hipLaunchKernelGGL(k_ng_rowsum, dim3(blocks(n)), dim3(256), 0, st, h->rowptr, h->wt, n, inv);
-    if (m > 0) hipLaunchKernelGGL(k_ng_scale, dim3(blocks(m)), dim3(256), 0, st, h->nbr, h->wt, inv, m, a);
+    hipLaunchKernelGGL(k_ng_rowsum, dim3(blocks(n)), dim3(256), 0, st, h->rowptr.p, h->wt.p, n, inv);
+    if (m > 0) hipLaunchKernelGGL(k_ng_scale, dim3(blocks(m)), dim3(256), 0, st, h->nbr.p, h->wt.p, inv, m, a);
     hipLaunchKernelGGL(k_ng_fill_f64, dim3(blocks(n)), dim3(256), 0, st, x, n, p);
     hipLaunchKernelGGL(k_ng_dangling, dim3((unsigned)nb), dim3(256), 0, st, x, inv, n, part + nb);
     hipLaunchKernelGGL(k_ng_final, dim3(1), dim3(256), 0, st, part + nb, nb, scal + 1);
     NgStep s{};
-    s.rowptr = h->rowptr; s.nbr = h->nbr; s.a = a; s.inv = inv; s.scal = scal; s.part = part;
+    s.rowptr = h->rowptr.p; s.nbr = h->nbr.p; s.a = a; s.inv = inv; s.scal = scal; s.part = part;
     s.alpha = alpha; s.p = p; s.omp = (1.0 - alpha) * p; s.n = n; s.nb = nb;
     for (int it = 0; it < max_iter && !converged; ++it) {
       s.x = x;
@@ -871,14 +845,13 @@ int anr_notegraph_pagerank(anr_notegraph *h, double alpha, int32_t max_iter, dou
     }
     ANR_HIP(hipGetLastError());
     if (converged) {
-      ANR_HIP(hipMemcpyAsync(h->cent, x, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+      ANR_HIP(hipMemcpyAsync(h->cent.p, x, (size_t)n * 8, hipMemcpyDeviceToDevice, st));
       if (out_host) ANR_HIP(hipMemcpyAsync(out_host, x, (size_t)n * 8, hipMemcpyDeviceToHost, st));
       ANR_HIP(hipStreamSynchronize(st));
     }
     return ANR_OK;
   };
-  int rc = body();
-  g_free(inv); g_free(a); g_free(x); g_free(xn); g_free(part); g_free(scal);
+  const int rc = body();
   if (iters) *iters = done;
   if (rc != ANR_OK) return rc;
   if (!converged) return fail(ANR_ENOCONV, "PageRank did not converge within %d iterations", (int)max_iter);
@@ -889,7 +862,7 @@ int anr_notegraph_set_centrality(anr_notegraph *h, const double *c_host) {
   if (!h || !c_host) return fail(ANR_EINVAL, "bad argument");
   std::lock_guard<std::mutex> lk(h->mu);
   DeviceGuard g(h->device);
-  ANR_HIP(hipMemcpyAsync(h->cent, c_host, (size_t)h->n * 8, hipMemcpyHostToDevice, h->stream));
+  ANR_HIP(hipMemcpyAsync(h->cent.p, c_host, (size_t)h->n * 8, hipMemcpyHostToDevice, h->stream));
   ANR_HIP(hipStreamSynchronize(h->stream));
   return ANR_OK;
 }
@@ -898,7 +871,7 @@ int anr_notegraph_get_centrality(anr_notegraph *h, double *c_host) {
   if (!h || !c_host) return fail(ANR_EINVAL, "bad argument");
   std::lock_guard<std::mutex> lk(h->mu);
   DeviceGuard g(h->device);
-  ANR_HIP(hipMemcpyAsync(c_host, h->cent, (size_t)h->n * 8, hipMemcpyDeviceToHost, h->stream));
+  ANR_HIP(hipMemcpyAsync(c_host, h->cent.p, (size_t)h->n * 8, hipMemcpyDeviceToHost, h->stream));
   ANR_HIP(hipStreamSynchronize(h->stream));
   return ANR_OK;
 }
@@ -907,7 +880,7 @@ int anr_notegraph_set_importance(anr_notegraph *h, const double *imp_host) {
   if (!h || !imp_host) return fail(ANR_EINVAL, "bad argument");
   std::lock_guard<std::mutex> lk(h->mu);
   DeviceGuard g(h->device);
-  ANR_HIP(hipMemcpyAsync(h->imp, imp_host, (size_t)h->n * 8, hipMemcpyHostToDevice, h->stream));
+  ANR_HIP(hipMemcpyAsync(h->imp.p, imp_host, (size_t)h->n * 8, hipMemcpyHostToDevice, h->stream));
   ANR_HIP(hipStreamSynchronize(h->stream));
   return ANR_OK;
 }
@@ -970,23 +943,23 @@ int anr_notegraph_components(anr_notegraph *h, int32_t *labels_host, int64_t *n_
   hipStream_t st = h->stream;
   const int64_t n = h->n;
   ANR_TRY(ensure_quality_small(h));
-  if (!h->q_label) ANR_TRY(g_alloc(&h->q_label, n));
-  hipLaunchKernelGGL(k_ng_iota_i32, dim3(blocks(n)), dim3(256), 0, st, h->q_label, n);
+  ANR_TRY(h->q_label.alloc(n, "note graph"));
+  hipLaunchKernelGGL(k_ng_iota_i32, dim3(blocks(n)), dim3(256), 0, st, h->q_label.p, n);
   for (int changed = h->m > 0; changed;) {
-    ANR_HIP(hipMemsetAsync(h->q_flag, 0, sizeof(int), st));
-    hipLaunchKernelGGL(k_ng_cc_hook, dim3(blocks(n * kNgLanes)), dim3(256), 0, st, h->rowptr, h->nbr, n, h->q_label,
-                       h->q_flag);
-    hipLaunchKernelGGL(k_ng_cc_flatten, dim3(blocks(n)), dim3(256), 0, st, h->q_label, n);
+    ANR_HIP(hipMemsetAsync(h->q_flag.p, 0, sizeof(int), st));
+    hipLaunchKernelGGL(k_ng_cc_hook, dim3(blocks(n * kNgLanes)), dim3(256), 0, st, h->rowptr.p, h->nbr.p, n, h->q_label.p,
+                       h->q_flag.p);
+    hipLaunchKernelGGL(k_ng_cc_flatten, dim3(blocks(n)), dim3(256), 0, st, h->q_label.p, n);
     ANR_HIP(hipGetLastError());
-    ANR_HIP(hipMemcpyAsync(&changed, h->q_flag, sizeof(int), hipMemcpyDeviceToHost, st));
+    ANR_HIP(hipMemcpyAsync(&changed, h->q_flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
     ANR_HIP(hipStreamSynchronize(st));
   }
   u64 roots = 0;
-  ANR_HIP(hipMemsetAsync(h->q_cnt + 2, 0, sizeof(u64), st));
-  hipLaunchKernelGGL(k_ng_cc_roots, dim3(blocks(n)), dim3(256), 0, st, h->q_label, n, h->q_cnt + 2);
+  ANR_HIP(hipMemsetAsync(h->q_cnt.p + 2, 0, sizeof(u64), st));
+  hipLaunchKernelGGL(k_ng_cc_roots, dim3(blocks(n)), dim3(256), 0, st, h->q_label.p, n, h->q_cnt.p + 2);
   ANR_HIP(hipGetLastError());
-  ANR_HIP(hipMemcpyAsync(&roots, h->q_cnt + 2, sizeof(u64), hipMemcpyDeviceToHost, st));
-  ANR_HIP(hipMemcpyAsync(labels_host, h->q_label, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  ANR_HIP(hipMemcpyAsync(&roots, h->q_cnt.p + 2, sizeof(u64), hipMemcpyDeviceToHost, st));
+  ANR_HIP(hipMemcpyAsync(labels_host, h->q_label.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   ANR_HIP(hipStreamSynchronize(st));
   if (n_components) *n_components = (int64_t)roots;
   return ANR_OK;
@@ -1014,50 +987,34 @@ int anr_notegraph_hop_histogram(anr_notegraph *h, int64_t n_sources, const int64
   ANR_TRY(ensure_quality_small(h));
   // words per node: the option or the default, halved while three state arrays do not fit half of the free memory
   int64_t W = h->bfs_words > 0 ? h->bfs_words : kNgBfsWords;
-  if (h->q_state_cap < 3 * n * W) {
-    g_free(h->q_state);
-    h->q_state_cap = 0;
+  if (h->q_state.cap < 3 * n * W) {
+    h->q_state.release();
     size_t free_b = 0, total_b = 0;
     ANR_HIP(hipMemGetInfo(&free_b, &total_b));
     while (W > 1 && (size_t)(3 * n * W) * 8 > free_b / 2) W /= 2;
-    ANR_TRY(g_alloc(&h->q_state, 3 * n * W));
-    h->q_state_cap = 3 * n * W;
+    ANR_TRY(h->q_state.alloc(3 * n * W, "note graph"));
   }
-  if (sources && h->q_src_cap < n_sources) {
-    g_free(h->q_src);
-    h->q_src_cap = 0;
-    ANR_TRY(g_alloc(&h->q_src, n_sources));
-    h->q_src_cap = n_sources;
-  }
+  if (sources && n_sources > 0) ANR_TRY(h->q_src.alloc(n_sources, "note graph"));
   if (sources && n_sources > 0)
-    ANR_HIP(hipMemcpyAsync(h->q_src, src32.data(), (size_t)n_sources * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    ANR_HIP(hipMemcpyAsync(h->q_src.p, src32.data(), (size_t)n_sources * sizeof(int32_t), hipMemcpyHostToDevice, st));
   const int64_t B = 64 * W, words = n * W;
   NgBfs p{};
-  p.rowptr = h->rowptr; p.nbr = h->nbr; p.n = n; p.W = (int)W; p.cnt = h->q_cnt;
+  p.rowptr = h->rowptr.p; p.nbr = h->nbr.p; p.n = n; p.W = (int)W; p.cnt = h->q_cnt.p;
   while ((1 << p.wshift) < W) p.wshift += 1;
-  p.seen = h->q_state;
-  u64 *fa = h->q_state + words, *fb = h->q_state + 2 * words;
+  p.seen = h->q_state.p;
+  u64 *fa = h->q_state.p + words, *fb = h->q_state.p + 2 * words;
   std::vector<int64_t> counts;
   if (n_sources > 0) counts.push_back(n_sources);
   int64_t passes = 0, walked = 0;
   int slot = 0;
-  struct Events {  // the call's span on the stream, for stats8[6]
-    hipEvent_t a = nullptr, b = nullptr;
-    ~Events() {
-      if (a) (void)hipEventDestroy(a);
-      if (b) (void)hipEventDestroy(b);
-    }
-  } ev;
-  if (stats8) {
-    ANR_HIP(hipEventCreate(&ev.a));
-    ANR_HIP(hipEventCreate(&ev.b));
-    ANR_HIP(hipEventRecord(ev.a, st));
-  }
-  ANR_HIP(hipMemsetAsync(h->q_cnt, 0, 2 * sizeof(u64), st));
+  Events<2> ev;  // the call's span on the stream, for stats8[6]
+  if (stats8) ANR_TRY(ev.init());
+  ANR_TRY(ev.mark(0, st));
+  ANR_HIP(hipMemsetAsync(h->q_cnt.p, 0, 2 * sizeof(u64), st));
   for (int64_t s0 = 0; s0 < n_sources; s0 += B, ++passes) {
     p.base = s0;
     p.nbits = std::min<int64_t>(B, n_sources - s0);
-    p.src = sources ? h->q_src + s0 : nullptr;
+    p.src = sources ? h->q_src.p + s0 : nullptr;
     ANR_HIP(hipMemsetAsync(p.seen, 0, (size_t)words * 8, st));
     ANR_HIP(hipMemsetAsync(fa, 0, (size_t)words * 8, st));
     hipLaunchKernelGGL(k_ng_bfs_seed, dim3(blocks(p.nbits)), dim3(256), 0, st, p, fa);
@@ -1067,7 +1024,7 @@ int anr_notegraph_hop_histogram(anr_notegraph *h, int64_t n_sources, const int64
       hipLaunchKernelGGL(k_ng_bfs_level, dim3(blocks(words)), dim3(256), 0, st, p);
       ANR_HIP(hipGetLastError());
       u64 added = 0;
-      ANR_HIP(hipMemcpyAsync(&added, h->q_cnt + slot, sizeof(u64), hipMemcpyDeviceToHost, st));
+      ANR_HIP(hipMemcpyAsync(&added, h->q_cnt.p + slot, sizeof(u64), hipMemcpyDeviceToHost, st));
       ANR_HIP(hipStreamSynchronize(st));
       slot ^= 1;
       walked += 1;
@@ -1079,9 +1036,9 @@ int anr_notegraph_hop_histogram(anr_notegraph *h, int64_t n_sources, const int64
   }
   if (stats8) {
     float ms = 0.0f;
-    ANR_HIP(hipEventRecord(ev.b, st));
-    ANR_HIP(hipEventSynchronize(ev.b));
-    ANR_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
+    ANR_TRY(ev.mark(1, st));
+    ANR_HIP(hipEventSynchronize(ev.e[1]));
+    ANR_TRY(ev.elapsed(0, 1, &ms));
     const int64_t st8[8] = {B, passes, walked, 3 * words * 8 + (sources ? n_sources * 4 : 0), W, n_sources,
                             (int64_t)((double)ms * 1000.0), 0};
     std::copy(st8, st8 + 8, stats8);
@@ -1109,8 +1066,7 @@ int anr_notegraph_set_option(anr_notegraph *h, int32_t option, int64_t value) {
       return fail(ANR_EINVAL, "BFS words per node must be 0 (default), 1, 2, 4, 8 or 16");
     DeviceGuard g(h->device);
     (void)hipStreamSynchronize(h->stream);
-    g_free(h->q_state);  // the next hop histogram sizes it for the new width
-    h->q_state_cap = 0;
+    h->q_state.release();  // the next hop histogram sizes it for the new width
     h->bfs_words = value;
     return ANR_OK;
   }

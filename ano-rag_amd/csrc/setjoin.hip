@@ -364,35 +364,25 @@ using namespace anr;
 struct anr_setjoin {
   int device = 0;
   int64_t n_rows = 0, n_items = 0, nnz = 0;
-  int64_t *indptr = nullptr, *post_ptr = nullptr;
-  int32_t *items = nullptr, *post_rows = nullptr;
+  DevBuf<int64_t> indptr, post_ptr;
+  DevBuf<int32_t> items, post_rows;
   hipStream_t stream = nullptr;
   std::mutex mu;
   int slots = kSjDefaultSlots;
   // the result of the last anr_setjoin_cooccur
   bool has_result = false;
   int64_t n_pairs = 0, n_common = 0;
-  int32_t *rI = nullptr, *rJ = nullptr, *rInter = nullptr, *rUni = nullptr, *rItems = nullptr;
-  int64_t *rPtr = nullptr;
+  DevBuf<int32_t> rI, rJ, rInter, rUni, rItems;
+  DevBuf<int64_t> rPtr;
 };
 
 namespace {
 
-template <typename T>
-int sj_alloc(T **p, int64_t n) {
-  *p = nullptr;
-  ANR_HIP(hipMalloc(reinterpret_cast<void **>(p), (size_t)(n > 0 ? n : 1) * sizeof(T)));
-  return ANR_OK;
-}
-template <typename T>
-void sj_free(T *&p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
 inline unsigned sj_blocks(int64_t n, int per = 256) { return (unsigned)std::max<int64_t>(1, ceil_div(n, per)); }
 
 void free_result(anr_setjoin *h) {
-  sj_free(h->rI); sj_free(h->rJ); sj_free(h->rInter); sj_free(h->rUni); sj_free(h->rItems); sj_free(h->rPtr);
+  for (auto *b : {&h->rI, &h->rJ, &h->rInter, &h->rUni, &h->rItems}) b->release();
+  h->rPtr.release();
   h->has_result = false;
   h->n_pairs = h->n_common = 0;
 }
@@ -433,37 +423,35 @@ int anr_setjoin_create(int64_t n_rows, int64_t n_items, const int64_t *indptr, c
   h->n_rows = n_rows;
   h->n_items = n_items;
   h->nnz = nnz;
-  u64 *k0 = nullptr, *k1 = nullptr;
-  unsigned *v0 = nullptr, *v1 = nullptr;
-  void *temp = nullptr;
-  auto body = [&]() -> int {
+  auto body = [&]() -> int {  // a failure destroys the handle below
+    DevBuf<u64> k0, k1;         // the sort's buffers, of this call only
+    DevBuf<unsigned> v0, v1;
+    DevBuf<unsigned char> temp;
     ANR_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     hipStream_t st = h->stream;
-    ANR_TRY(sj_alloc(&h->indptr, n_rows + 1));
-    ANR_TRY(sj_alloc(&h->items, nnz));
-    ANR_TRY(sj_alloc(&h->post_ptr, n_items + 1));
-    ANR_TRY(sj_alloc(&h->post_rows, nnz));
-    ANR_HIP(hipMemcpyAsync(h->indptr, indptr, (size_t)(n_rows + 1) * 8, hipMemcpyHostToDevice, st));
+    ANR_TRY(h->indptr.alloc(n_rows + 1, "setjoin"));
+    ANR_TRY(h->items.alloc(nnz, "setjoin"));
+    ANR_TRY(h->post_ptr.alloc(n_items + 1, "setjoin"));
+    ANR_TRY(h->post_rows.alloc(nnz, "setjoin"));
+    ANR_HIP(hipMemcpyAsync(h->indptr.p, indptr, (size_t)(n_rows + 1) * 8, hipMemcpyHostToDevice, st));
     if (nnz > 0) {
-      ANR_HIP(hipMemcpyAsync(h->items, items, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
-      ANR_TRY(sj_alloc(&k0, nnz));
-      ANR_TRY(sj_alloc(&k1, nnz));
-      ANR_TRY(sj_alloc(&v0, nnz));
-      ANR_TRY(sj_alloc(&v1, nnz));
-      ANR_HIP(hipMalloc(&temp, radix_sort_temp_bytes(nnz)));
-      ANR_HIP(hipMemsetAsync(v0, 0, (size_t)nnz * 4, st));  // the sort carries a value per key; the keys are all there is
-      hipLaunchKernelGGL(k_sj_keys, dim3(sj_blocks(nnz)), dim3(256), 0, st, h->indptr, h->items, n_rows, nnz, k0);
-      ANR_TRY(radix_sort_pairs_u64(temp, k0, k1, v0, v1, nnz, false, st));
-      hipLaunchKernelGGL(k_sj_post_rows, dim3(sj_blocks(nnz)), dim3(256), 0, st, k1, nnz, h->post_rows);
+      ANR_HIP(hipMemcpyAsync(h->items.p, items, (size_t)nnz * 4, hipMemcpyHostToDevice, st));
+      ANR_TRY(k0.alloc(nnz, "setjoin"));
+      ANR_TRY(k1.alloc(nnz, "setjoin"));
+      ANR_TRY(v0.alloc(nnz, "setjoin"));
+      ANR_TRY(v1.alloc(nnz, "setjoin"));
+      ANR_TRY(temp.alloc((int64_t)radix_sort_temp_bytes(nnz), "setjoin"));
+      ANR_HIP(hipMemsetAsync(v0.p, 0, (size_t)nnz * 4, st));  // the sort carries a value per key; the keys are all there is
+      hipLaunchKernelGGL(k_sj_keys, dim3(sj_blocks(nnz)), dim3(256), 0, st, h->indptr.p, h->items.p, n_rows, nnz, k0.p);
+      ANR_TRY(radix_sort_pairs_u64(temp.p, k0.p, k1.p, v0.p, v1.p, nnz, false, st));
+      hipLaunchKernelGGL(k_sj_post_rows, dim3(sj_blocks(nnz)), dim3(256), 0, st, k1.p, nnz, h->post_rows.p);
     }
-    hipLaunchKernelGGL(k_sj_post_ptr, dim3(sj_blocks(n_items + 1)), dim3(256), 0, st, k1, nnz, n_items, h->post_ptr);
+    hipLaunchKernelGGL(k_sj_post_ptr, dim3(sj_blocks(n_items + 1)), dim3(256), 0, st, k1.p, nnz, n_items, h->post_ptr.p);
     ANR_HIP(hipGetLastError());
     ANR_HIP(hipStreamSynchronize(st));
     return ANR_OK;
   };
-  int rc = body();
-  sj_free(k0); sj_free(k1); sj_free(v0); sj_free(v1);
-  if (temp) (void)hipFree(temp);
+  const int rc = body();
   if (rc != ANR_OK) {
     anr_setjoin_destroy(h);
     return rc;
@@ -477,9 +465,8 @@ int anr_setjoin_destroy(anr_setjoin *h) {
   DeviceGuard g(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   free_result(h);
-  sj_free(h->indptr); sj_free(h->items); sj_free(h->post_ptr); sj_free(h->post_rows);
   if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
+  delete h;  // frees the rows and the postings, still under the guard
   return ANR_OK;
 }
 
@@ -509,32 +496,32 @@ int anr_setjoin_cooccur(anr_setjoin *h, int32_t min_common, int64_t *n_pairs, in
   int log_s = 0;
   while ((1 << log_s) < S) ++log_s;
   const int lds = sj_lds_bytes(S);
-  int64_t *row_pairs = nullptr, *row_common = nullptr, *pair_off = nullptr, *common_off = nullptr;
-  int32_t *row_passes = nullptr;
-  u64 *d_stats = nullptr;
   u64 hs[kSjStN] = {0};
   int64_t tot[2] = {0, 0};
   const int64_t scratch = n > 0 && h->nnz > 0 ? (n * 2 + (n + 1) * 2) * 8 + n * 4 + kSjStN * 8 : 0;
-  auto body = [&]() -> int {
+  auto body = [&]() -> int {  // a failure frees the partial result below
     if (n == 0 || h->nnz == 0) return ANR_OK;
-    ANR_TRY(sj_alloc(&row_pairs, n));
-    ANR_TRY(sj_alloc(&row_common, n));
-    ANR_TRY(sj_alloc(&row_passes, n));
-    ANR_TRY(sj_alloc(&pair_off, n + 1));
-    ANR_TRY(sj_alloc(&common_off, n + 1));
-    ANR_TRY(sj_alloc(&d_stats, kSjStN));
-    ANR_HIP(hipMemsetAsync(d_stats, 0, kSjStN * 8, st));
+    DevBuf<int64_t> row_pairs, row_common, pair_off, common_off;  // scratch of this call
+    DevBuf<int32_t> row_passes;
+    DevBuf<u64> d_stats;
+    ANR_TRY(row_pairs.alloc(n, "setjoin"));
+    ANR_TRY(row_common.alloc(n, "setjoin"));
+    ANR_TRY(row_passes.alloc(n, "setjoin"));
+    ANR_TRY(pair_off.alloc(n + 1, "setjoin"));
+    ANR_TRY(common_off.alloc(n + 1, "setjoin"));
+    ANR_TRY(d_stats.alloc(kSjStN, "setjoin"));
+    ANR_HIP(hipMemsetAsync(d_stats.p, 0, kSjStN * 8, st));
     ANR_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(&k_sj_cooccur<false>), sj_lds_bytes(kSjMaxSlots)));
     ANR_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(&k_sj_cooccur<true>), sj_lds_bytes(kSjMaxSlots)));
     SjOut none{};
-    hipLaunchKernelGGL((k_sj_cooccur<false>), dim3((unsigned)n), dim3(kSjThreads), lds, st, n, h->indptr, h->items, h->post_ptr,
-                       h->post_rows, (unsigned)min_common, S, log_s, row_pairs, row_common, row_passes, nullptr, nullptr, none,
-                       d_stats);
-    hipLaunchKernelGGL(k_sj_scan, dim3(1), dim3(1024), 0, st, row_pairs, n, pair_off);
-    hipLaunchKernelGGL(k_sj_scan, dim3(1), dim3(1024), 0, st, row_common, n, common_off);
+    hipLaunchKernelGGL((k_sj_cooccur<false>), dim3((unsigned)n), dim3(kSjThreads), lds, st, n, h->indptr.p, h->items.p,
+                       h->post_ptr.p, h->post_rows.p, (unsigned)min_common, S, log_s, row_pairs.p, row_common.p, row_passes.p,
+                       nullptr, nullptr, none, d_stats.p);
+    hipLaunchKernelGGL(k_sj_scan, dim3(1), dim3(1024), 0, st, row_pairs.p, n, pair_off.p);
+    hipLaunchKernelGGL(k_sj_scan, dim3(1), dim3(1024), 0, st, row_common.p, n, common_off.p);
     ANR_HIP(hipGetLastError());
-    ANR_HIP(hipMemcpyAsync(&tot[0], pair_off + n, 8, hipMemcpyDeviceToHost, st));
-    ANR_HIP(hipMemcpyAsync(&tot[1], common_off + n, 8, hipMemcpyDeviceToHost, st));
+    ANR_HIP(hipMemcpyAsync(&tot[0], pair_off.p + n, 8, hipMemcpyDeviceToHost, st));
+    ANR_HIP(hipMemcpyAsync(&tot[1], common_off.p + n, 8, hipMemcpyDeviceToHost, st));
     ANR_HIP(hipStreamSynchronize(st));
     // the output: 16 bytes + an offset per pair, 4 bytes per shared item — an error when it does not fit, never a cut
     const int64_t need = tot[0] * 24 + 8 + tot[1] * 4;
@@ -543,25 +530,24 @@ int anr_setjoin_cooccur(anr_setjoin *h, int32_t min_common, int64_t *n_pairs, in
     if ((u64)need > (u64)free_b)
       return fail(ANR_EHIP, "co-occurrence result does not fit: %lld pairs and %lld shared items need %lld bytes, %lld are free "
                   "on the device; raise min_common", (long long)tot[0], (long long)tot[1], (long long)need, (long long)free_b);
-    ANR_TRY(sj_alloc(&h->rI, tot[0]));
-    ANR_TRY(sj_alloc(&h->rJ, tot[0]));
-    ANR_TRY(sj_alloc(&h->rInter, tot[0]));
-    ANR_TRY(sj_alloc(&h->rUni, tot[0]));
-    ANR_TRY(sj_alloc(&h->rPtr, tot[0] + 1));
-    ANR_TRY(sj_alloc(&h->rItems, tot[1]));
-    SjOut o{h->rI, h->rJ, h->rInter, h->rUni, h->rPtr, h->rItems, tot[0], tot[1]};
-    hipLaunchKernelGGL((k_sj_cooccur<true>), dim3((unsigned)n), dim3(kSjThreads), lds, st, n, h->indptr, h->items, h->post_ptr,
-                       h->post_rows, (unsigned)min_common, S, log_s, row_pairs, row_common, row_passes, pair_off, common_off, o,
-                       d_stats);
+    ANR_TRY(h->rI.alloc(tot[0], "setjoin"));
+    ANR_TRY(h->rJ.alloc(tot[0], "setjoin"));
+    ANR_TRY(h->rInter.alloc(tot[0], "setjoin"));
+    ANR_TRY(h->rUni.alloc(tot[0], "setjoin"));
+    ANR_TRY(h->rPtr.alloc(tot[0] + 1, "setjoin"));
+    ANR_TRY(h->rItems.alloc(tot[1], "setjoin"));
+    SjOut o{h->rI.p, h->rJ.p, h->rInter.p, h->rUni.p, h->rPtr.p, h->rItems.p, tot[0], tot[1]};
+    hipLaunchKernelGGL((k_sj_cooccur<true>), dim3((unsigned)n), dim3(kSjThreads), lds, st, n, h->indptr.p, h->items.p,
+                       h->post_ptr.p, h->post_rows.p, (unsigned)min_common, S, log_s, row_pairs.p, row_common.p, row_passes.p,
+                       pair_off.p, common_off.p, o, d_stats.p);
     ANR_HIP(hipGetLastError());
-    ANR_HIP(hipMemcpyAsync(h->rPtr + tot[0], &tot[1], 8, hipMemcpyHostToDevice, st));
-    ANR_HIP(hipMemcpyAsync(hs, d_stats, kSjStN * 8, hipMemcpyDeviceToHost, st));
+    ANR_HIP(hipMemcpyAsync(h->rPtr.p + tot[0], &tot[1], 8, hipMemcpyHostToDevice, st));
+    ANR_HIP(hipMemcpyAsync(hs, d_stats.p, kSjStN * 8, hipMemcpyDeviceToHost, st));
     ANR_HIP(hipStreamSynchronize(st));
     if (hs[kSjStBroken]) return fail(ANR_EINTERNAL, "co-occurrence: the fill launch disagreed with the count launch on %llu rows", hs[kSjStBroken]);
     return ANR_OK;
   };
-  int rc = body();
-  sj_free(row_pairs); sj_free(row_common); sj_free(row_passes); sj_free(pair_off); sj_free(common_off); sj_free(d_stats);
+  const int rc = body();
   if (rc != ANR_OK) {
     free_result(h);
     return rc;
@@ -598,12 +584,12 @@ int anr_setjoin_cooccur_fetch(anr_setjoin *h, int32_t *I, int32_t *J, int32_t *i
   if (!I || !J || !inter || !uni || (nc > 0 && !common_items)) return fail(ANR_EINVAL, "null output array");
   DeviceGuard g(h->device);
   hipStream_t st = h->stream;
-  ANR_HIP(hipMemcpyAsync(I, h->rI, (size_t)np * 4, hipMemcpyDeviceToHost, st));
-  ANR_HIP(hipMemcpyAsync(J, h->rJ, (size_t)np * 4, hipMemcpyDeviceToHost, st));
-  ANR_HIP(hipMemcpyAsync(inter, h->rInter, (size_t)np * 4, hipMemcpyDeviceToHost, st));
-  ANR_HIP(hipMemcpyAsync(uni, h->rUni, (size_t)np * 4, hipMemcpyDeviceToHost, st));
-  ANR_HIP(hipMemcpyAsync(common_ptr, h->rPtr, (size_t)(np + 1) * 8, hipMemcpyDeviceToHost, st));
-  if (nc > 0) ANR_HIP(hipMemcpyAsync(common_items, h->rItems, (size_t)nc * 4, hipMemcpyDeviceToHost, st));
+  ANR_HIP(hipMemcpyAsync(I, h->rI.p, (size_t)np * 4, hipMemcpyDeviceToHost, st));
+  ANR_HIP(hipMemcpyAsync(J, h->rJ.p, (size_t)np * 4, hipMemcpyDeviceToHost, st));
+  ANR_HIP(hipMemcpyAsync(inter, h->rInter.p, (size_t)np * 4, hipMemcpyDeviceToHost, st));
+  ANR_HIP(hipMemcpyAsync(uni, h->rUni.p, (size_t)np * 4, hipMemcpyDeviceToHost, st));
+  ANR_HIP(hipMemcpyAsync(common_ptr, h->rPtr.p, (size_t)(np + 1) * 8, hipMemcpyDeviceToHost, st));
+  if (nc > 0) ANR_HIP(hipMemcpyAsync(common_items, h->rItems.p, (size_t)nc * 4, hipMemcpyDeviceToHost, st));
   ANR_HIP(hipStreamSynchronize(st));
   return ANR_OK;
 }
@@ -619,24 +605,20 @@ int anr_setjoin_pair_counts(anr_setjoin *h, int64_t n, const int32_t *I, const i
   std::lock_guard<std::mutex> lk(h->mu);
   DeviceGuard g(h->device);
   hipStream_t st = h->stream;
-  int32_t *dI = nullptr, *dJ = nullptr, *dA = nullptr, *dU = nullptr;
-  auto body = [&]() -> int {
-    ANR_TRY(sj_alloc(&dI, n));
-    ANR_TRY(sj_alloc(&dJ, n));
-    ANR_TRY(sj_alloc(&dA, n));
-    ANR_TRY(sj_alloc(&dU, n));
-    ANR_HIP(hipMemcpyAsync(dI, I, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    ANR_HIP(hipMemcpyAsync(dJ, J, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_sj_pair_counts, dim3(sj_blocks(n * kSjPairLanes)), dim3(256), 0, st, n, dI, dJ, h->indptr, h->items, dA, dU);
-    ANR_HIP(hipGetLastError());
-    ANR_HIP(hipMemcpyAsync(inter, dA, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    ANR_HIP(hipMemcpyAsync(uni, dU, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-    ANR_HIP(hipStreamSynchronize(st));
-    return ANR_OK;
-  };
-  int rc = body();
-  sj_free(dI); sj_free(dJ); sj_free(dA); sj_free(dU);
-  return rc;
+  DevBuf<int32_t> dI, dJ, dA, dU;  // of this call
+  ANR_TRY(dI.alloc(n, "setjoin"));
+  ANR_TRY(dJ.alloc(n, "setjoin"));
+  ANR_TRY(dA.alloc(n, "setjoin"));
+  ANR_TRY(dU.alloc(n, "setjoin"));
+  ANR_HIP(hipMemcpyAsync(dI.p, I, (size_t)n * 4, hipMemcpyHostToDevice, st));
+  ANR_HIP(hipMemcpyAsync(dJ.p, J, (size_t)n * 4, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_sj_pair_counts, dim3(sj_blocks(n * kSjPairLanes)), dim3(256), 0, st, n, dI.p, dJ.p, h->indptr.p,
+                     h->items.p, dA.p, dU.p);
+  ANR_HIP(hipGetLastError());
+  ANR_HIP(hipMemcpyAsync(inter, dA.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  ANR_HIP(hipMemcpyAsync(uni, dU.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  ANR_HIP(hipStreamSynchronize(st));
+  return ANR_OK;
 }
 
 }  // extern "C"

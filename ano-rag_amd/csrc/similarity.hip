@@ -109,32 +109,27 @@ extern "C" int anr_similarity_matrix(int32_t device, const float *a_host, int64_
   const size_t ab = (size_t)m * d * 4, bb = (size_t)n * d * 4, ob = (size_t)m * n * 8;
   const size_t o_b = round_up((int64_t)ab, 256), o_da = o_b + round_up((int64_t)bb, 256), o_db = o_da + round_up(m * 4, 256),
                o_out = o_db + round_up(n * 4, 256);
-  unsigned char *D = nullptr;
-  ANR_HIP(hipMalloc(reinterpret_cast<void **>(&D), o_out + ob));
-  int rc = ANR_OK;
-  auto run = [&]() -> int {
-    ANR_HIP(hipMemcpy(D, a_host, ab, hipMemcpyHostToDevice));
-    ANR_HIP(hipMemcpy(D + o_b, b_host, bb, hipMemcpyHostToDevice));
-    SimParams p{};
-    p.a = reinterpret_cast<const float *>(D);
-    p.b = reinterpret_cast<const float *>(D + o_b);
-    p.m = m; p.n = n; p.d = d; p.metric = metric;
-    p.out = reinterpret_cast<double *>(D + o_out);
-    if (metric == 0) {
-      float *da = reinterpret_cast<float *>(D + o_da), *db = reinterpret_cast<float *>(D + o_db);
-      hipLaunchKernelGGL(k_sim_denoms, dim3((unsigned)ceil_div(m, 4)), dim3(256), 0, nullptr, p.a, m, d, da);
-      hipLaunchKernelGGL(k_sim_denoms, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, nullptr, p.b, n, d, db);
-      p.da = da;
-      p.db = db;
-    }
-    const int64_t gx = ceil_div(n, kSimTile), gy = ceil_div(m, kSimTile);
-    if (gy > 65535) return fail(ANR_EINVAL, "too many rows in the first set (%lld)", (long long)m);
-    hipLaunchKernelGGL(k_similarity, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, nullptr, p);
-    ANR_HIP(hipGetLastError());
-    ANR_HIP(hipMemcpy(out_host, D + o_out, ob, hipMemcpyDeviceToHost));
-    return ANR_OK;
-  };
-  rc = run();
-  (void)hipFree(D);
-  return rc;
+  DevBuf<unsigned char> buf;
+  ANR_TRY(buf.alloc((int64_t)(o_out + ob), "similarity matrix"));
+  unsigned char *D = buf.p;
+  ANR_HIP(hipMemcpy(D, a_host, ab, hipMemcpyHostToDevice));
+  ANR_HIP(hipMemcpy(D + o_b, b_host, bb, hipMemcpyHostToDevice));
+  SimParams p{};
+  p.a = reinterpret_cast<const float *>(D);
+  p.b = reinterpret_cast<const float *>(D + o_b);
+  p.m = m; p.n = n; p.d = d; p.metric = metric;
+  p.out = reinterpret_cast<double *>(D + o_out);
+  if (metric == 0) {
+    float *da = reinterpret_cast<float *>(D + o_da), *db = reinterpret_cast<float *>(D + o_db);
+    hipLaunchKernelGGL(k_sim_denoms, dim3((unsigned)ceil_div(m, 4)), dim3(256), 0, nullptr, p.a, m, d, da);
+    hipLaunchKernelGGL(k_sim_denoms, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0, nullptr, p.b, n, d, db);
+    p.da = da;
+    p.db = db;
+  }
+  const int64_t gx = ceil_div(n, kSimTile), gy = ceil_div(m, kSimTile);
+  if (gy > 65535) return fail(ANR_EINVAL, "too many rows in the first set (%lld)", (long long)m);
+  hipLaunchKernelGGL(k_similarity, dim3((unsigned)gx, (unsigned)gy), dim3(256), 0, nullptr, p);
+  ANR_HIP(hipGetLastError());
+  ANR_HIP(hipMemcpy(out_host, D + o_out, ob, hipMemcpyDeviceToHost));
+  return ANR_OK;
 }
