@@ -8,8 +8,14 @@ on the host: O(N^2 d) for the k-distance curve and again for DBSCAN.  Here both 
 * ``dbscan_labels`` is ``anr_index_dbscan``: the MFMA self join's tile walk with the eps pairs consumed where they are
   produced (degree, union and border pass).  The labels are sklearn's, label for label.
 
-``hdbscan`` (the reference's default) is not provided: its result is not a function of the data alone (tie order in the
-spanning tree); it stays on sklearn, and ``cluster_labels`` keeps refusing it and ``kmeans``.
+``hdbscan`` (the reference's default, :73-79) has names of its own: ``hdbscan_mst`` is ``anr_index_hdbscan_mst``, the two
+O(N^2 d) passes on the stored rows (core distances, then Prim's spanning tree of the mutual-reachability distance, both
+sklearn's float64 bit for bit), ``hdbscan_labels`` adds the tree stage on the host (``anr_hdbscan_labels``)
+and ``hdbscan_topic_labels`` is what the reference's branch returns.  One step of sklearn's is not a function of the data:
+it orders the tree's edges with an unstable ``np.argsort``, so edges of equal weight come in an order that neither the data
+nor the code defines.  Here the order is defined: a stable sort, equal weights keep Prim's order.  Where the reference's
+labels hang on that order, ours are the stable-order ones (behavioural differences).  ``cluster_labels``
+keeps refusing ``hdbscan`` and ``kmeans``: it is the ``dbscan`` branch.
 
 K-means has names of its own.  The reference fixes ``random_state=42`` and every draw sklearn makes is independent of the
 data, so the host draws them all up front (``kmeans_draws``) and ``anr_index_kmeans`` runs the rest on the stored rows
@@ -46,6 +52,11 @@ STATS_NAMES = ("n_clusters", "n_core", "n_noise", "n_rescored", "tile_walks", "j
 KMEANS_STATS_NAMES = ("lloyd_iterations", "assignment_passes", "seeding_steps", "scratch_bytes", "mfma_steps_per_tile",
                       "emptied_init", "strict_inits", "tol")
 KMEANS_MAX_CLUSTERS = 64
+HDBSCAN_MAX_MIN_SAMPLES = 16
+HDBSCAN_STATS_NAMES = ("prim_steps", "core_tiles", "scratch_bytes", "partials_per_step", "core_us", "prim_us",
+                       "reserved6", "reserved7")
+HDBSCAN_TREE_STATS_NAMES = ("n_clusters", "n_noise", "condensed_clusters", "tied_edges", "true_splits", "rows_through_eps",
+                            "reserved6", "reserved7")
 QUALITY_STATS_NAMES = ("n_labels", "n_noise", "silhouette_tiles", "cohesion_tiles", "n_cohesion_clusters",
                        "scratch_bytes", "mfma_steps_per_tile", "reserved")
 
@@ -282,6 +293,107 @@ def fallback_labels(embeddings, device: int = 0) -> np.ndarray:
     return kmeans_fit(emb, n_clusters, 1, 42, device)[0]
 
 
+def hdbscan_mst(embeddings_or_index, min_samples: int = 3, device: int = 0, return_stats: bool = False):
+    """What sklearn's ``HDBSCAN(min_samples=min_samples, metric='euclidean')`` computes before its tree stage:
+    ``(core, src, dst, w)`` — the float64 core distances [N] (the ``min_samples``-th smallest distance of a row, itself
+    included) and the N - 1 edges of Prim's spanning tree of ``max(core_a, core_b, dist)`` from row 0, in the order they
+    are added (int64, int64, float64), all bit-equal to sklearn's.  Given an array, a temporary L2 index is built; a
+    ``FlatIndex`` must be an L2 one that does not normalise its rows; its rows stay on the device (they are checked for
+    NaN and infinities there, before either pass).  ``ValueError`` before either pass for fewer than 2 rows,
+    ``min_samples`` outside 1 .. min(``HDBSCAN_MAX_MIN_SAMPLES``, N), and rows that are not finite (sklearn's handling of
+    infinite rows stays on sklearn).  The index is locked for the whole call.  ``return_stats=True`` adds a dict (``HDBSCAN_STATS_NAMES``)."""
+    ms = int(min_samples)
+    if ms < 1:
+        raise ValueError(f"min_samples={ms} must be at least 1")
+    if ms > HDBSCAN_MAX_MIN_SAMPLES:
+        raise ValueError(f"min_samples={ms} is above the {HDBSCAN_MAX_MIN_SAMPLES} the device core distances keep")
+    own = not isinstance(embeddings_or_index, FlatIndex)
+    if own:
+        rows = np.ascontiguousarray(embeddings_or_index, dtype=np.float32)
+        if rows.ndim != 2:
+            raise ValueError(f"expected an [N, d] array of embeddings, got shape {rows.shape}")
+        n = rows.shape[0]
+    else:
+        index = embeddings_or_index
+        if index.metric != METRIC_L2 or index.normalize:
+            raise ValueError("hdbscan runs on the rows as given: it needs an L2 index without normalisation")
+        n = index.ntotal
+        rows = None
+    if n < 2:
+        raise ValueError(f"n_samples={n}: hdbscan needs at least 2 rows")
+    if ms > n:
+        raise ValueError(f"min_samples ({ms}) must be at most the number of samples in X ({n})")
+    if rows is not None and not np.isfinite(rows).all():  # the rows of an index are looked at on the device
+        raise ValueError("the rows hold NaN or infinite values: keep sklearn for such an input")
+    if own:
+        index = _own_index(rows, "euclidean", device)
+    try:
+        core = np.empty((n,), dtype=np.float64)
+        src = np.empty((n - 1,), dtype=np.int64)
+        dst = np.empty((n - 1,), dtype=np.int64)
+        w = np.empty((n - 1,), dtype=np.float64)
+        stats = np.zeros((8,), dtype=np.int64)
+        rc = index._lib.anr_index_hdbscan_mst(index._h, ms, core.ctypes.data, src.ctypes.data, dst.ctypes.data,
+                                              w.ctypes.data, stats.ctypes.data)
+        if rc == -1 and "NaN or infinite" in _lib.last_error():
+            raise ValueError("the rows hold NaN or infinite values: keep sklearn for such an input")
+        _lib.check(rc, "anr_index_hdbscan_mst")
+    finally:
+        if own:
+            index.close()
+    if return_stats:
+        return core, src, dst, w, dict(zip(HDBSCAN_STATS_NAMES, (int(v) for v in stats)))
+    return core, src, dst, w
+
+
+def hdbscan_tree_labels(src, dst, w, min_cluster_size: int = 5, cluster_selection_epsilon: float = 0.0,
+                        return_stats: bool = False):
+    """``anr_hdbscan_labels`` as it is (host only, no device needed): int64 labels [N], -1 for noise, from the N - 1 edges
+    of a spanning tree — sklearn's single linkage, condensed tree, stability, excess of mass and epsilon search, with equal
+    weights kept in the order given.  ``ValueError`` for what the library refuses."""
+    src = np.ascontiguousarray(src, dtype=np.int64)
+    dst = np.ascontiguousarray(dst, dtype=np.int64)
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    if not (src.ndim == dst.ndim == w.ndim == 1 and src.shape == dst.shape == w.shape):
+        raise ValueError(f"expected three arrays of N - 1 edges, got shapes {src.shape}, {dst.shape}, {w.shape}")
+    n = int(w.shape[0]) + 1
+    labels = np.empty((n,), dtype=np.int32)
+    stats = np.zeros((8,), dtype=np.int64)
+    lib = _lib.load()
+    rc = lib.anr_hdbscan_labels(n, src.ctypes.data, dst.ctypes.data, w.ctypes.data, int(min_cluster_size),
+                                C.c_double(float(cluster_selection_epsilon)), labels.ctypes.data, stats.ctypes.data)
+    if rc == -1:
+        raise ValueError(_lib.last_error())
+    _lib.check(rc, "anr_hdbscan_labels")
+    out = labels.astype(np.int64)
+    if return_stats:
+        return out, dict(zip(HDBSCAN_TREE_STATS_NAMES, (int(v) for v in stats)))
+    return out
+
+
+def hdbscan_labels(embeddings_or_index, min_cluster_size: int = 5, min_samples=None, cluster_selection_epsilon: float = 0.0,
+                   device: int = 0, return_stats: bool = False):
+    """sklearn's ``HDBSCAN(min_cluster_size, min_samples, metric='euclidean', cluster_selection_epsilon).fit_predict`` of
+    the rows with the stable tie order: int64 labels, -1 for noise.  ``min_samples=None`` means ``min_cluster_size``, as in
+    sklearn.  ``hdbscan_mst`` on the device, then ``hdbscan_tree_labels`` on the host.  Only ``eom`` selection without
+    ``allow_single_cluster`` and ``max_cluster_size``; no ``probabilities_``, no medoids."""
+    mcs = int(min_cluster_size)
+    if mcs < 2:
+        raise ValueError(f"min_cluster_size={mcs} must be at least 2")
+    ms = mcs if min_samples is None else int(min_samples)
+    got = hdbscan_mst(embeddings_or_index, ms, device, return_stats)
+    labels = hdbscan_tree_labels(got[1], got[2], got[3], mcs, cluster_selection_epsilon, return_stats)
+    if return_stats:
+        return labels[0], {**got[4], **labels[1]}
+    return labels
+
+
+def hdbscan_topic_labels(embeddings, min_cluster_size: int = 5, min_samples: int = 3, device: int = 0) -> np.ndarray:
+    """What ``_cpu_clustering`` returns for ``clustering.algorithm: hdbscan``, the reference's default (:73-79, :99):
+    ``HDBSCAN(min_cluster_size, min_samples, metric='euclidean', cluster_selection_epsilon=0.1).fit_predict``."""
+    return hdbscan_labels(embeddings, min_cluster_size, min_samples, 0.1, device)
+
+
 def _int32_labels(labels, n: int) -> np.ndarray:
     lab = np.asarray(labels)
     if lab.ndim != 1 or lab.shape[0] != n:
@@ -401,4 +513,5 @@ def analyze_clusters(embeddings, labels, device: int = 0) -> dict:
 __all__ = ["dbscan_labels", "find_optimal_eps", "cluster_labels", "EPS_INFLATION", "STATS_NAMES", "analyze_clusters",
            "silhouette_samples", "silhouette_score", "cluster_cohesion", "cluster_quality", "QUALITY_STATS_NAMES", "kmeans_fit",
            "kmeans_draws", "find_optimal_k", "kmeans_topic_labels", "fallback_labels", "EmptyClusterError",
-           "KMEANS_STATS_NAMES", "KMEANS_MAX_CLUSTERS"]
+           "KMEANS_STATS_NAMES", "KMEANS_MAX_CLUSTERS", "hdbscan_mst", "hdbscan_tree_labels", "hdbscan_labels",
+           "hdbscan_topic_labels", "HDBSCAN_MAX_MIN_SAMPLES", "HDBSCAN_STATS_NAMES", "HDBSCAN_TREE_STATS_NAMES"]

@@ -251,6 +251,36 @@ int anr_index_kmeans(anr_index *h, int32_t k, int32_t n_init, int32_t n_local_tr
                      const double *uniforms, int32_t max_iter, double tol_scale, int32_t *labels, double *centres,
                      double *inertia, int32_t *n_iter, int32_t *best_init, int64_t *stats);
 
+/* HDBSCAN's two O(N^2 d) passes on the stored rows: what sklearn 1.7's HDBSCAN(min_samples, metric='euclidean') computes
+ * before its tree stage — the default branch of TopicClustering._cpu_clustering (doc/clustering.py:73-79).  L2 index
+ * without normalisation only (ANR_EINVAL otherwise).  The distance is float64 sqrt(sum_k (x_k - y_k) * (x_k - y_k)), k
+ * ascending, no fused operation, a correctly rounded root: sklearn's bit for bit.
+ *   core[i]: the min_samples-th smallest distance of row i to all rows, itself included (1 <= min_samples <=
+ *   HDBSCAN_MAX_MIN_SAMPLES and <= ntotal; ANR_EINVAL beyond).
+ *   src / dst / w [ntotal - 1]: Prim's algorithm from row 0 over max(core[a], core[b], dist(a, b)); the row added next is
+ *   the one with the smallest (value, row), so equal values go to the lowest row; edge i joins src[i], already in the tree,
+ *   to dst[i].  One kernel launch per step on the handle's stream, none waits for the host.
+ * ntotal >= 2 (ANR_EINVAL otherwise).  The rows must be finite: a device pass looks before either pass starts, and a NaN or
+ * an infinity ends the call with ANR_EINVAL and nothing written.  The handle's lock is held for the whole call, the N - 1
+ * launches and the final synchronisation included — seconds at 20 000 rows, minutes at 100 000 — and every other call on
+ * the handle waits that long.  All outputs are host arrays.  stats (8 words, may be NULL): [0] Prim steps, [1] 64 x 64 tiles of the core-distance pass, [2] bytes of device
+ * scratch of the call, [3] workgroup partials reduced per step, [4] / [5] microseconds of the core-distance pass and of
+ * the Prim steps on the device (HIP events, created only when stats is given; 0 where they cannot be read). */
+#define HDBSCAN_MAX_MIN_SAMPLES 16
+int anr_index_hdbscan_mst(anr_index *h, int32_t min_samples, double *core, int64_t *src, int64_t *dst, double *w,
+                          int64_t *stats);
+
+/* HDBSCAN's tree stage, on the host (no device is touched): labels [n] (int32, -1 noise) from the n - 1 edges of a spanning
+ * tree, as sklearn's HDBSCAN(min_cluster_size, cluster_selection_epsilon = eps, cluster_selection_method = 'eom',
+ * allow_single_cluster = False) derives them — single linkage, condensed tree, stability, excess of mass, the epsilon
+ * search, labels by ascending cluster id — with edges of equal weight kept in the order given (a stable sort), where
+ * sklearn's np.argsort leaves their order open.  ANR_EINVAL for n < 2, min_cluster_size < 2, a negative eps, an edge that
+ * names no row, a weight that is negative or not finite, and edges that close a cycle.  stats (8 words, may be NULL):
+ * [0] clusters, [1] noise rows, [2] clusters of the condensed tree (the root included), [3] edges whose weight equals
+ * their predecessor's in the sorted order, [4] true splits, [5] rows labelled through an ancestor that eps chose. */
+int anr_hdbscan_labels(int64_t n, const int64_t *src, const int64_t *dst, const double *w, int32_t min_cluster_size,
+                       double eps, int32_t *labels, int64_t *stats);
+
 /* tuning / introspection */
 #define ANR_OPT_FORCE_EXACT 1     /* 1: skip the f16 scan, run the dense exact path for every query  */
 #define ANR_OPT_OVERFETCH 2       /* candidates kept per query before the exact re-score (0 = auto)  */
