@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <vector>
@@ -371,7 +372,19 @@ int launch_scan(anr_index *h, const ScanParams &p, hipStream_t st, int max_grid,
   if (grid_out) *grid_out = (int)grid;
   // a pass over more than the Infinity Cache can hold streams with non-temporal loads
   const bool stream = p.tile_stride == 1 && p.n_tiles * (int64_t)p.kb * 1024 > ((int64_t)192 << 20);
+#if defined(ANR_SCAN8_AB)
+  const char *ab_env = std::getenv("ANR_SCAN8_AB");
+  const bool ab = BITS == 8 && ab_env && ab_env[0] == '1';
+#define ANR_LAUNCH_SCAN8_AB(CHV, STRV)                                                                             \
+  if (ab) {                                                                                                        \
+    ANR_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(k_scan8_ab<DENSE, CHV, 768, STRV>), 160 * 1024));   \
+    hipLaunchKernelGGL((k_scan8_ab<DENSE, CHV, 768, STRV>), dim3((unsigned)grid), dim3(nt), lds, st, p);          \
+  } else
+#else
+#define ANR_LAUNCH_SCAN8_AB(CHV, STRV)
+#endif
 #define ANR_LAUNCH_SCAN(CHV, STRV)                                                                                 \
+  ANR_LAUNCH_SCAN8_AB(CHV, STRV)                                                                                   \
   if (BITS == 8) {                                                                                                 \
     ANR_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(k_scan8<DENSE, CHV, 768, STRV>), 160 * 1024));      \
     hipLaunchKernelGGL((k_scan8<DENSE, CHV, 768, STRV>), dim3((unsigned)grid), dim3(nt), lds, st, p);             \
@@ -385,6 +398,7 @@ int launch_scan(anr_index *h, const ScanParams &p, hipStream_t st, int max_grid,
     if (stream) ANR_LAUNCH_SCAN(4, true) else ANR_LAUNCH_SCAN(4, false)
   }
 #undef ANR_LAUNCH_SCAN
+#undef ANR_LAUNCH_SCAN8_AB
   ANR_HIP(hipGetLastError());
   return ANR_OK;
 }

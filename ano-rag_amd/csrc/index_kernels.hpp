@@ -12,13 +12,11 @@
 //                                      elements 4-7, and the eight low nibbles (elements 0-3 in the low nibbles of bytes
 //                                      0-3, elements 4-7 in the high nibbles) — seven vector instructions turn them back
 //                                      into the 16-byte f16 operand (x12_unpack);
-//   x8   [cap/32][KB/2 pairs][64][16 B] + [32 rows][KB/2] f16
+//   x8   [cap/32][KB/8 granules][4352 B]
 //                                      optional (ANR_OPT_SCAN_BITS 8): int8 codes with one f16 scale per row and 32 dims (a
-//                                      pair of k-blocks), 1.0625 B per value.  A tile is kb * 544 bytes: first the codes,
-//                                      per pair 64 lanes x 16 B — lane l = r + 32 h holds row r's elements 8h..8h+7 of the
-//                                      pair's first k-block (bytes 0-7), then of its second (bytes 8-15), each code c stored
-//                                      as the byte c + 128 — then the scales, row-major: row r's scale of pair m at byte
-//                                      kb * 512 + r * kb + 2 m of the tile.  Decoded value f16(s * c) (x8_operand);
+//                                      pair of k-blocks), 1.0625 B per value; every eight k-blocks' codes are followed by
+//                                      their scales (the layout is described at kX8TileBytesPerKb).  Decoded value
+//                                      f16(s * c) (x8_operand);
 //   q16  [2][KB][64 lanes][8]          f16, the 64 queries of a batch in the B-operand layout.
 // KB = dimp/16 with dimp = dim rounded up to 128.
 #pragma once
@@ -105,7 +103,23 @@ __device__ __forceinline__ uint4 x12_unpack(unsigned h0, unsigned h1, unsigned n
 // Per row and 32-dim group: s = f16(absmax / 127), one f16 step up if s * 127 < absmax (an all-zero group keeps s = 0);
 // c = clamp(rint(x / s), -cmax, cmax) with cmax = min(127, floor(65504 / s)) so that s * c stays finite; decoded value
 // f16(s * c), one rounding.
+//
+// Layout.  A 32-row tile is kb * kX8TileBytesPerKb bytes: kb / 8 granules of kX8GranuleBytes = 4352 (kb is a multiple of 8),
+// one per eight k-blocks (128 dims), each holding everything the scan needs for those k-blocks, in the order it reads it:
+//   bytes 0 .. 4095     the codes of the granule's four pairs of k-blocks, per pair 64 lanes x 16 B: lane l = r + 32 h holds
+//                       row r's elements 8 h .. 8 h + 7 of the pair's first k-block (bytes 0-7), then of its second (bytes
+//                       8-15), each code c stored as the byte c + 128;
+//   bytes 4096 .. 4351  the scales [32 rows][4] f16: row r's scale of the granule's pair j at byte 4096 + 8 r + 2 j.
+// Pair m of a row (dims 32 m .. 32 m + 31) is pair m & 3 of granule m >> 2 (x8_pair, x8_scale_at).  Granules and their
+// scale blocks start 256-byte aligned, and a scan reads every byte of a tile exactly once, in address order.
 constexpr int kX8TileBytesPerKb = 544;  // codes 512 + scales 32 per k-block of a 32-row tile
+constexpr int kX8GranuleBytes = 8 * kX8TileBytesPerKb;
+constexpr int kX8GranuleCodeBytes = 8 * 512;
+// byte offsets in a tile: the 1-KiB code block of pair m, and row r's scale of pair m
+__host__ __device__ __forceinline__ int64_t x8_pair(int m) { return (int64_t)(m >> 2) * kX8GranuleBytes + (m & 3) * 1024; }
+__host__ __device__ __forceinline__ int64_t x8_scale_at(int m, int r) {
+  return (int64_t)(m >> 2) * kX8GranuleBytes + kX8GranuleCodeBytes + r * 8 + (m & 3) * 2;
+}
 __device__ __forceinline__ unsigned short x8_scale(float absmax) {
   _Float16 s = (_Float16)(absmax / 127.0f);
   if ((float)s * 127.0f < absmax) {
@@ -293,9 +307,9 @@ __global__ __launch_bounds__(256) void k_add(AddParams p) {
         const float e8 = x8_group(&s_x[r][g * 32], 1, &sb, &lo, &hi);
         const int m = (k0 >> 5) + g;
         unsigned char *t = p.x8 + tile * p.kb * kX8TileBytesPerKb;
-        *reinterpret_cast<uint4 *>(t + (int64_t)m * 1024 + r * 16) = lo;
-        *reinterpret_cast<uint4 *>(t + (int64_t)m * 1024 + (r + 32) * 16) = hi;
-        *reinterpret_cast<unsigned short *>(t + (int64_t)p.kb * 512 + r * p.kb + 2 * m) = sb;
+        *reinterpret_cast<uint4 *>(t + x8_pair(m) + r * 16) = lo;
+        *reinterpret_cast<uint4 *>(t + x8_pair(m) + (r + 32) * 16) = hi;
+        *reinterpret_cast<unsigned short *>(t + x8_scale_at(m, r)) = sb;
         atomicAdd(&s_err8[r], e8);
       }
     }
@@ -385,9 +399,9 @@ __global__ __launch_bounds__(256) void k_build8(Build8Params p) {
     unsigned short sb;
     uint4 lo, hi;
     const float e8 = x8_group(v, 1, &sb, &lo, &hi);
-    *reinterpret_cast<uint4 *>(t + (int64_t)m * 1024 + r * 16) = lo;
-    *reinterpret_cast<uint4 *>(t + (int64_t)m * 1024 + (r + 32) * 16) = hi;
-    *reinterpret_cast<unsigned short *>(t + (int64_t)p.kb * 512 + r * p.kb + 2 * m) = sb;
+    *reinterpret_cast<uint4 *>(t + x8_pair(m) + r * 16) = lo;
+    *reinterpret_cast<uint4 *>(t + x8_pair(m) + (r + 32) * 16) = hi;
+    *reinterpret_cast<unsigned short *>(t + x8_scale_at(m, r)) = sb;
     if (grow < p.n_rows) atomicAdd(&s_err8[r], e8);
   }
   __syncthreads();
@@ -420,8 +434,8 @@ __global__ __launch_bounds__(256) void k_image_rows(ImageRowsParams p) {
     hv = __builtin_bit_cast(half8, x12_unpack(w[0], w[1], w[2]));
   } else if (p.x8) {
     const unsigned char *t = p.x8 + tile * p.kb * kX8TileBytesPerKb;
-    const unsigned *w = reinterpret_cast<const unsigned *>(t + (int64_t)(kbl >> 1) * 1024 + l * 16 + (kbl & 1) * 8);
-    const unsigned short sb = *reinterpret_cast<const unsigned short *>(t + (int64_t)p.kb * 512 + (l & 31) * p.kb + 2 * (kbl >> 1));
+    const unsigned *w = reinterpret_cast<const unsigned *>(t + x8_pair(kbl >> 1) + l * 16 + (kbl & 1) * 8);
+    const unsigned short sb = *reinterpret_cast<const unsigned short *>(t + x8_scale_at(kbl >> 1, l & 31));
     hv = x8_operand(w[0], w[1], __builtin_bit_cast(half2v, (unsigned)sb | ((unsigned)sb << 16)));
   } else {
     hv = *reinterpret_cast<const half8 *>(p.x16 + (blk * 64 + l) * 8);
@@ -629,16 +643,18 @@ __device__ __forceinline__ void scan_mfma_refill(ScanOp<F12> (&a)[CH], const cha
 }
 
 // A chunk of CH k-blocks of one tile, as the k-loop of the scan sees it: `x` is the lane's pointer to the chunk's codes,
-// `sx` to its scales (8-bit image only; kScaleOffset(kb, lane) from the codes of a tile's first chunk, kScaleChunkBytes per
-// chunk).  The f16 and 12-bit images: CH ScanOps, no scales.
+// `sx` to its scales (8-bit image only).  Chunk c of a tile starts chunk_off(c) bytes after the tile's first chunk, its scales
+// scale_off(c) bytes after the first chunk's, which sit kScaleOffset(lane) bytes after the lane's first codes.  The f16 and
+// 12-bit images: CH ScanOps, no scales.
 template <int CH, bool F12>
 struct ScanChunk {
   ScanOp<F12> a[CH];
   static constexpr int kLaneBytes = ScanOp<F12>::kLaneBytes;
   static constexpr int64_t kTileBytesPerKb = 64 * kLaneBytes;
   static constexpr int64_t kChunkBytes = CH * 64 * kLaneBytes;
-  static constexpr int64_t kScaleChunkBytes = 0;
-  static __device__ __forceinline__ int kScaleOffset(int, int) { return 0; }
+  static __device__ __forceinline__ int64_t chunk_off(int c) { return c * kChunkBytes; }
+  static __device__ __forceinline__ int64_t scale_off(int) { return 0; }
+  static __device__ __forceinline__ int kScaleOffset(int) { return 0; }
   template <bool STREAM>
   __device__ __forceinline__ void load(const char *x, const char *) {
     scan_load<CH, STREAM, F12>(a, x);
@@ -652,10 +668,12 @@ struct ScanChunk {
     scan_mfma_refill<CH, STREAM, F12>(a, x, ldsq0, ldsq1, kbase, acc0, acc1);
   }
 };
-// The 8-bit image: CH / 2 pairs of k-blocks, 16 bytes of codes each, and the row's CH / 2 f16 scales of the chunk (one
-// 8- or 4-byte load from the tile's scale block).  The operand is decoded right before its two MFMAs (x8_operand); the
-// next chunk's scales are requested first, so its first pair never waits behind its codes.
-template <int CH>
+// The 8-bit image: CH / 2 pairs of k-blocks, 16 bytes of codes each, and the row's CH / 2 f16 scales of the chunk: one 8-byte
+// load from the scale block of the chunk's own granule (CH 8), or the 4-byte half of it (CH 4: two chunks per granule).
+// The operand is decoded right before its two MFMAs (x8_operand); the next chunk's scales are requested first, so its first
+// pair never waits behind its codes.
+constexpr bool kScan8ScalesNT = true;  // the scale words of a streaming pass carry the non-temporal hint (see load_scales)
+template <int CH, bool SNT = kScan8ScalesNT>
 struct ScanChunk8 {
   static_assert(CH == 8 || CH == 4, "chunks of 4 or 8 k-blocks");
   typedef unsigned su __attribute__((ext_vector_type(CH / 4)));
@@ -663,17 +681,25 @@ struct ScanChunk8 {
   su sc;
   static constexpr int kLaneBytes = 16;
   static constexpr int64_t kTileBytesPerKb = kX8TileBytesPerKb;
-  static constexpr int64_t kChunkBytes = CH * 512;
-  static constexpr int64_t kScaleChunkBytes = CH;  // CH / 2 scales of 2 bytes
-  // the lane's scales of a tile's first chunk minus its codes of that chunk (both in the tile): kb * 512 + row * kb - lane * 16
-  static __device__ __forceinline__ int kScaleOffset(int kb, int lane) { return kb * 512 + (lane & 31) * kb - lane * 16; }
-  // The scales keep the default cache policy even in a streaming pass: a tile's scale block (kb * 32 bytes, 12 lines of
-  // 128 B at kb 48) is read once per chunk, 8 or 4 bytes per row each time, so every chunk touches all of its lines.  With
-  // the non-temporal hint those lines left the L2 between chunks and came from HBM again: 1.17 x the algorithmic bytes
-  // per 10 M-row pass, against 1.00 x with the lines kept (DESIGN.md §4 "Round 8").
+  static constexpr int64_t kChunkBytes = CH * 512;      // codes
+  static constexpr int64_t kScaleChunkBytes = CH;       // CH / 2 scales of 2 bytes per row
+  static constexpr int kPerGranule = 8 / CH;            // chunks per granule
+  static __device__ __forceinline__ int64_t chunk_off(int c) {
+    return (int64_t)(c / kPerGranule) * kX8GranuleBytes + (c % kPerGranule) * kChunkBytes;
+  }
+  static __device__ __forceinline__ int64_t scale_off(int c) {
+    return (int64_t)(c / kPerGranule) * kX8GranuleBytes + (c % kPerGranule) * kScaleChunkBytes;
+  }
+  // the lane's scales of a tile's first chunk minus its codes of that chunk: the granule's scale block, 8 bytes per row
+  static __device__ __forceinline__ int kScaleOffset(int lane) { return kX8GranuleCodeBytes + (lane & 31) * 8 - lane * 16; }
+  // A chunk's scale words sit right behind the codes they scale (kX8TileBytesPerKb), in two 128-byte lines that no other
+  // chunk touches, so like the codes they are read from HBM once whatever the cache policy: the policy no longer decides the
+  // HBM traffic, as it did while every chunk of a tile touched all lines of one scale block per tile (DESIGN.md §4 "Round 8"
+  // and "Round 15").  In a streaming pass they carry the codes' non-temporal hint.
   template <bool STREAM>
   static __device__ __forceinline__ su load_scales(const char *sx) {
-    return *reinterpret_cast<const su *>(sx);
+    const su *p = reinterpret_cast<const su *>(sx);
+    return (STREAM && SNT) ? __builtin_nontemporal_load(p) : *p;
   }
   template <bool STREAM>
   __device__ __forceinline__ void load_code(const char *x, int j) {
@@ -802,9 +828,8 @@ __device__ __forceinline__ void scan_body(const ScanParams &p, const char *image
   // always has loads in flight (the epilogue would otherwise be a bubble in its share of the stream)
   C aA, aB;
   // a tile is kb * C::kTileBytesPerKb bytes; the lane's pointer into it is offset by lane * C::kLaneBytes
-  constexpr int64_t CB = C::kChunkBytes, SB = C::kScaleChunkBytes;
   const int64_t tbytes = p.kb * C::kTileBytesPerKb;
-  const int soff = C::kScaleOffset(p.kb, lane);
+  const int soff = C::kScaleOffset(lane);
   const char *xlane = image + lane * C::kLaneBytes;
   if (wglobal < p.n_tiles) {
     const char *x0 = xlane + (p.tile0 + wglobal * p.tile_stride) * tbytes;
@@ -816,8 +841,8 @@ __device__ __forceinline__ void scan_body(const ScanParams &p, const char *image
     // no next tile: re-request this tile's last chunk instead (an L2 hit), which keeps the loop free of
     // conditional loads so the compiler can count the outstanding loads exactly
     const bool more = i + wtotal < p.n_tiles;
-    const char *xn = more ? xa + wtotal * p.tile_stride * tbytes : xa + (int64_t)(nch - 1) * CB;
-    const char *sn = more ? sa + wtotal * p.tile_stride * tbytes : sa + (int64_t)(nch - 1) * SB;
+    const char *xn = more ? xa + wtotal * p.tile_stride * tbytes : xa + C::chunk_off(nch - 1);
+    const char *sn = more ? sa + wtotal * p.tile_stride * tbytes : sa + C::scale_off(nch - 1);
     floatx16 acc0, acc1;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -825,10 +850,10 @@ __device__ __forceinline__ void scan_body(const ScanParams &p, const char *image
       acc1[r] = 0.0f;
     }
     for (int c = 0; c < nch; c += 2) {
-      aB.template load<STREAM>(xa + (int64_t)(c + 1) * CB, sa + (int64_t)(c + 1) * SB);
+      aB.template load<STREAM>(xa + C::chunk_off(c + 1), sa + C::scale_off(c + 1));
       __builtin_amdgcn_sched_barrier(0);
       const bool in = c + 2 < nch;
-      aA.template mfma_refill<STREAM>(in ? xa + (int64_t)(c + 2) * CB : xn, in ? sa + (int64_t)(c + 2) * SB : sn, ldsq0, ldsq1,
+      aA.template mfma_refill<STREAM>(in ? xa + C::chunk_off(c + 2) : xn, in ? sa + C::scale_off(c + 2) : sn, ldsq0, ldsq1,
                                       c * CH, acc0, acc1);
       __builtin_amdgcn_sched_barrier(0);
       aB.mfma(ldsq0, ldsq1, (c + 1) * CH, acc0, acc1);
@@ -915,6 +940,13 @@ template <bool DENSE, int CH, int NT, bool STREAM>
 __global__ __launch_bounds__(NT) ANR_SCAN_ATTR void k_scan8(ScanParams p) {
   scan_body<DENSE, CH, ScanChunk8<CH>, STREAM>(p, reinterpret_cast<const char *>(p.x8));
 }
+#if defined(ANR_SCAN8_AB)  // developer A/B build: the same scan with the other cache policy for the scale words, launched
+// instead of k_scan8 while the environment variable ANR_SCAN8_AB is set to 1 (tools/scan8_policy_ab.py)
+template <bool DENSE, int CH, int NT, bool STREAM>
+__global__ __launch_bounds__(NT) ANR_SCAN_ATTR void k_scan8_ab(ScanParams p) {
+  scan_body<DENSE, CH, ScanChunk8<CH, !kScan8ScalesNT>, STREAM>(p, reinterpret_cast<const char *>(p.x8));
+}
+#endif
 
 // ------------------------------------------------------------------------------------------------
 // sample (shadow form of k_scan<DENSE> + groupmax): the threshold sample of batch i + 1 computed BESIDE the resident

@@ -39,14 +39,17 @@ R, O, ROUND = sys.argv[1:4]
 out = {}
 for c in ("FETCH_SIZE", "WRITE_SIZE"):
     f = glob.glob(f"{O}/pmc_{c}/*/*counter_collection.csv")[0]
-    rows = [r for r in csv.DictReader(open(f)) if "k_scan<false" in r["Kernel_Name"] and r["Counter_Name"] == c]
+    allrows = [r for r in csv.DictReader(open(f)) if r["Counter_Name"] == c]
+    # the main scan of the 10 M-row batches: k_scan8 (the 8-bit image, the automatic choice at this size), else k_scan
+    rows = [r for r in allrows if "k_scan8<false" in r["Kernel_Name"]] or [r for r in allrows if "k_scan<false" in r["Kernel_Name"]]
     out[c] = [float(r["Counter_Value"]) for r in rows]
     kernel = rows[0]["Kernel_Name"]
     with open(f"{O}/{ROUND}_pmc_{c}_k_scan.csv", "w", newline="") as o:
         w = csv.DictWriter(o, fieldnames=list(rows[0].keys())); w.writeheader(); w.writerows(rows)
 fetch = sum(out["FETCH_SIZE"]) / len(out["FETCH_SIZE"]); write = sum(out["WRITE_SIZE"]) / len(out["WRITE_SIZE"])
 rows_n, dim = 10_000_000, 768
-bpv = 1.5 if ", true, true>" in kernel else 2.0   # k_scan<DENSE, CH, NT, STREAM, F12>: the 12-bit image
+# k_scan8: codes + one f16 scale per 32 values; k_scan<DENSE, CH, NT, STREAM, F12>: the 12-bit or the f16 image
+bpv = 1.0625 if "k_scan8<" in kernel else (1.5 if ", true, true>" in kernel else 2.0)
 traffic = (2 * fetch + write) * 1024
 sys.path.insert(0, f"{R}/tools")
 from scan_source_hash import scan_source_sha256
