@@ -373,13 +373,22 @@ int launch_scan(anr_index *h, const ScanParams &p, hipStream_t st, int max_grid,
   // a pass over more than the Infinity Cache can hold streams with non-temporal loads
   const bool stream = p.tile_stride == 1 && p.n_tiles * (int64_t)p.kb * 1024 > ((int64_t)192 << 20);
 #if defined(ANR_SCAN8_AB)
+  // developer A/B build: 1 the other cache policy of the scale words; 2 ... 6 arm sets of ScanChunk8 (2 is the unpipelined loop;
+  // tools/scan8_arms_ab.py names them)
   const char *ab_env = std::getenv("ANR_SCAN8_AB");
-  const bool ab = BITS == 8 && ab_env && ab_env[0] == '1';
-#define ANR_LAUNCH_SCAN8_AB(CHV, STRV)                                                                             \
-  if (ab) {                                                                                                        \
-    ANR_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(k_scan8_ab<DENSE, CHV, 768, STRV>), 160 * 1024));   \
-    hipLaunchKernelGGL((k_scan8_ab<DENSE, CHV, 768, STRV>), dim3((unsigned)grid), dim3(nt), lds, st, p);          \
+  const int ab = BITS == 8 && ab_env ? std::atoi(ab_env) : 0;
+#define ANR_LAUNCH_SCAN8_FORM(N, CHV, STRV, SNT, ARMS)                                                             \
+  if (ab == N) {                                                                                                   \
+    ANR_TRY(ensure_dynamic_lds(reinterpret_cast<const void *>(k_scan8_ab<DENSE, CHV, 768, STRV, SNT, ARMS>), 160 * 1024)); \
+    hipLaunchKernelGGL((k_scan8_ab<DENSE, CHV, 768, STRV, SNT, ARMS>), dim3((unsigned)grid), dim3(nt), lds, st, p); \
   } else
+#define ANR_LAUNCH_SCAN8_AB(CHV, STRV)                                                                             \
+  ANR_LAUNCH_SCAN8_FORM(1, CHV, STRV, !kScan8ScalesNT, kScan8Arms)                                                 \
+  ANR_LAUNCH_SCAN8_FORM(2, CHV, STRV, kScan8ScalesNT, 0)                                                           \
+  ANR_LAUNCH_SCAN8_FORM(3, CHV, STRV, kScan8ScalesNT, kArmSplat)                                                   \
+  ANR_LAUNCH_SCAN8_FORM(4, CHV, STRV, kScan8ScalesNT, kArmSplat | kArmDecAhead)                                    \
+  ANR_LAUNCH_SCAN8_FORM(5, CHV, STRV, kScan8ScalesNT, kArmSplat | kArmPrio)                                        \
+  ANR_LAUNCH_SCAN8_FORM(6, CHV, STRV, kScan8ScalesNT, kArmPrio)
 #else
 #define ANR_LAUNCH_SCAN8_AB(CHV, STRV)
 #endif
@@ -399,6 +408,7 @@ int launch_scan(anr_index *h, const ScanParams &p, hipStream_t st, int max_grid,
   }
 #undef ANR_LAUNCH_SCAN
 #undef ANR_LAUNCH_SCAN8_AB
+#undef ANR_LAUNCH_SCAN8_FORM
   ANR_HIP(hipGetLastError());
   return ANR_OK;
 }

@@ -152,9 +152,13 @@ __device__ __forceinline__ half8 x8_operand(unsigned w0, unsigned w1, half2v ss)
   o[4] = o2[0]; o[5] = o2[1]; o[6] = o3[0]; o[7] = o3[1];
   return o;
 }
-// {s, s} from the scale half `hi` of a word holding two scales
+// {s, s} from the scale half `hi` of a word holding two scales.  FOLD: written as a shuffle of the word's two halves, which
+// with a constant `hi` folds into the op_sel / op_sel_hi modifiers of the v_pk_mul_f16 that uses it; else one v_perm_b32.
+template <bool FOLD>
 __device__ __forceinline__ half2v x8_splat(unsigned w, int hi) {
-  return __builtin_bit_cast(half2v, __builtin_amdgcn_perm(w, w, hi ? 0x03020302u : 0x01000100u));
+  if (!FOLD) return __builtin_bit_cast(half2v, __builtin_amdgcn_perm(w, w, hi ? 0x03020302u : 0x01000100u));
+  const half2v v = __builtin_bit_cast(half2v, w);
+  return hi ? half2v{v[1], v[1]} : half2v{v[0], v[0]};
 }
 // one row's 32-value group (v[0..31] = dims 32 m .. 32 m + 31, zeros past the row) -> its scale bits, the two 16-byte lane
 // words (lane r: dims 0-7 and 16-23; lane r + 32: dims 8-15 and 24-31) and the squared error of the decoded values
@@ -655,35 +659,56 @@ struct ScanChunk {
   static __device__ __forceinline__ int64_t chunk_off(int c) { return c * kChunkBytes; }
   static __device__ __forceinline__ int64_t scale_off(int) { return 0; }
   static __device__ __forceinline__ int kScaleOffset(int) { return 0; }
+  struct Pipe {};  // nothing is carried from one k-block to the next (see ScanChunk8::Pipe)
+  static __device__ __forceinline__ void prime(Pipe &, const ScanChunk &) {}
   template <bool STREAM>
   __device__ __forceinline__ void load(const char *x, const char *) {
     scan_load<CH, STREAM, F12>(a, x);
   }
-  __device__ __forceinline__ void mfma(const uint4 *ldsq0, const uint4 *ldsq1, int kbase, floatx16 &acc0, floatx16 &acc1) {
+  __device__ __forceinline__ void mfma(Pipe &, const ScanChunk &, const uint4 *ldsq0, const uint4 *ldsq1, int kbase,
+                                       floatx16 &acc0, floatx16 &acc1) {
     scan_mfma<CH, F12>(a, ldsq0, ldsq1, kbase, acc0, acc1);
   }
   template <bool STREAM>
-  __device__ __forceinline__ void mfma_refill(const char *x, const char *, const uint4 *ldsq0, const uint4 *ldsq1, int kbase,
-                                              floatx16 &acc0, floatx16 &acc1) {
+  __device__ __forceinline__ void mfma_refill(Pipe &, const ScanChunk &, const char *x, const char *, const uint4 *ldsq0,
+                                              const uint4 *ldsq1, int kbase, floatx16 &acc0, floatx16 &acc1) {
     scan_mfma_refill<CH, STREAM, F12>(a, x, ldsq0, ldsq1, kbase, acc0, acc1);
   }
 };
 // The 8-bit image: CH / 2 pairs of k-blocks, 16 bytes of codes each, and the row's CH / 2 f16 scales of the chunk: one 8-byte
 // load from the scale block of the chunk's own granule (CH 8), or the 4-byte half of it (CH 4: two chunks per granule).
-// The operand is decoded right before its two MFMAs (x8_operand); the next chunk's scales are requested first, so its first
-// pair never waits behind its codes.
+// The next chunk's scales are requested first, so its first pair never waits behind its codes.
+//
+// The k-loop is software-pipelined by hand (DESIGN.md §4 "Round 16").  ARMS says which parts; the shipped set is kScan8Arms,
+// the developer A/B build (k_scan8_ab) instantiates the others, the unpipelined loop (ARMS 0) among them:
+//   kArmSplat     the scale splat folds into the multiply's operand select (x8_splat<true>);
+//   kArmDecAhead  the operand of k-block t + 1 is decoded (x8_operand) between and behind the two MFMAs of k-block t, into
+//                 Pipe::av, so no MFMA waits for a multiply issued right in front of it;
+//   kArmPrio      the wave runs at priority 1 from a k-block's first MFMA to its second, at 0 behind it: of the three waves of
+//                 a SIMD the one that has an MFMA ready gets the issue slot, the others' decodes fill the MFMA's shadow.
+// The decoded operand carries over chunk and tile boundaries: the one after a chunk's last k-block is the first of chunk `nxt`
+// (the other buffer, which by then holds the following chunk, of this tile or of the wave's next).  The arithmetic of a
+// k-block and the order in which k-blocks enter the accumulators are those of the unpipelined loop.
+enum { kArmSplat = 1, kArmDecAhead = 2, kArmPrio = 4 };
+constexpr int kScan8Arms = kArmSplat | kArmDecAhead | kArmPrio;
 constexpr bool kScan8ScalesNT = true;  // the scale words of a streaming pass carry the non-temporal hint (see load_scales)
-template <int CH, bool SNT = kScan8ScalesNT>
+template <int CH, bool SNT = kScan8ScalesNT, int ARMS = kScan8Arms>
 struct ScanChunk8 {
   static_assert(CH == 8 || CH == 4, "chunks of 4 or 8 k-blocks");
   typedef unsigned su __attribute__((ext_vector_type(CH / 4)));
   uint4 code[CH / 2];
   su sc;
+  static constexpr bool kDecAhead = (ARMS & kArmDecAhead) != 0;
   static constexpr int kLaneBytes = 16;
   static constexpr int64_t kTileBytesPerKb = kX8TileBytesPerKb;
   static constexpr int64_t kChunkBytes = CH * 512;      // codes
   static constexpr int64_t kScaleChunkBytes = CH;       // CH / 2 scales of 2 bytes per row
   static constexpr int kPerGranule = 8 / CH;            // chunks per granule
+  // what the k-loop carries from one k-block to the next: the decoded operand of the coming k-block (untouched, and no
+  // register, without kArmDecAhead)
+  struct Pipe {
+    half8 av;
+  };
   static __device__ __forceinline__ int64_t chunk_off(int c) {
     return (int64_t)(c / kPerGranule) * kX8GranuleBytes + (c % kPerGranule) * kChunkBytes;
   }
@@ -711,31 +736,49 @@ struct ScanChunk8 {
 #pragma unroll
     for (int j = 0; j < CH / 2; ++j) load_code<STREAM>(x, j);
   }
-  __device__ __forceinline__ void pair_mfma(const uint4 &w, half2v ss, const uint4 *ldsq0, const uint4 *ldsq1, int kb0,
-                                            floatx16 &acc0, floatx16 &acc1) const {
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const uint4 b0 = ldsq0[(kb0 + h) * 64];
-      const uint4 b1 = ldsq1[(kb0 + h) * 64];
-      const half8 av = h ? x8_operand(w.z, w.w, ss) : x8_operand(w.x, w.y, ss);
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, __builtin_bit_cast(half8, b0), acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, __builtin_bit_cast(half8, b1), acc1, 0, 0, 0);
-    }
+  static __device__ __forceinline__ half2v pair_scale(const su &s, int j) {
+    return x8_splat<(ARMS & kArmSplat) != 0>(s[j >> 1], j & 1);
   }
-  __device__ __forceinline__ void mfma(const uint4 *ldsq0, const uint4 *ldsq1, int kbase, floatx16 &acc0, floatx16 &acc1) {
-#pragma unroll
-    for (int j = 0; j < CH / 2; ++j) pair_mfma(code[j], x8_splat(sc[j >> 1], j & 1), ldsq0, ldsq1, kbase + 2 * j, acc0, acc1);
+  // before a wave's first k-block: the first operand of chunk `first` (its loads are waited for)
+  static __device__ __forceinline__ void prime(Pipe &s, const ScanChunk8 &first) {
+    if (kDecAhead) s.av = x8_operand(first.code[0].x, first.code[0].y, pair_scale(first.sc, 0));
   }
-  template <bool STREAM>
-  __device__ __forceinline__ void mfma_refill(const char *x, const char *sx, const uint4 *ldsq0, const uint4 *ldsq1, int kbase,
-                                              floatx16 &acc0, floatx16 &acc1) {
-    const su cur = sc;
-    sc = load_scales<STREAM>(sx);
+  // the chunk's CH k-blocks with the scales `cur`; REFILL: each pair's code register is re-filled from `x` behind the pair
+  template <bool REFILL, bool STREAM>
+  __device__ __forceinline__ void run(Pipe &s, const ScanChunk8 &nxt, const su cur, const char *x, const uint4 *ldsq0,
+                                      const uint4 *ldsq1, int kbase, floatx16 &acc0, floatx16 &acc1) {
 #pragma unroll
     for (int j = 0; j < CH / 2; ++j) {
-      pair_mfma(code[j], x8_splat(cur[j >> 1], j & 1), ldsq0, ldsq1, kbase + 2 * j, acc0, acc1);
-      load_code<STREAM>(x, j);
+      const half2v ss = pair_scale(cur, j);
+      const uint4 w = code[j];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const uint4 b0 = ldsq0[(kbase + 2 * j + h) * 64];
+        const uint4 b1 = ldsq1[(kbase + 2 * j + h) * 64];
+        const half8 av = kDecAhead ? s.av : (h ? x8_operand(w.z, w.w, ss) : x8_operand(w.x, w.y, ss));
+        if (ARMS & kArmPrio) __builtin_amdgcn_s_setprio(1);
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, __builtin_bit_cast(half8, b0), acc0, 0, 0, 0);
+        if (kDecAhead) {
+          if (h == 0) s.av = x8_operand(w.z, w.w, ss);
+          else if (j + 1 < CH / 2) s.av = x8_operand(code[j + 1].x, code[j + 1].y, pair_scale(cur, j + 1));
+          else s.av = x8_operand(nxt.code[0].x, nxt.code[0].y, pair_scale(nxt.sc, 0));
+        }
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, __builtin_bit_cast(half8, b1), acc1, 0, 0, 0);
+        if (ARMS & kArmPrio) __builtin_amdgcn_s_setprio(0);
+      }
+      if (REFILL) load_code<STREAM>(x, j);
     }
+  }
+  __device__ __forceinline__ void mfma(Pipe &s, const ScanChunk8 &nxt, const uint4 *ldsq0, const uint4 *ldsq1, int kbase,
+                                       floatx16 &acc0, floatx16 &acc1) {
+    run<false, false>(s, nxt, sc, nullptr, ldsq0, ldsq1, kbase, acc0, acc1);
+  }
+  template <bool STREAM>
+  __device__ __forceinline__ void mfma_refill(Pipe &s, const ScanChunk8 &nxt, const char *x, const char *sx, const uint4 *ldsq0,
+                                              const uint4 *ldsq1, int kbase, floatx16 &acc0, floatx16 &acc1) {
+    const su cur = sc;
+    sc = load_scales<STREAM>(sx);
+    run<true, STREAM>(s, nxt, cur, x, ldsq0, ldsq1, kbase, acc0, acc1);
   }
 };
 
@@ -827,6 +870,7 @@ __device__ __forceinline__ void scan_body(const ScanParams &p, const char *image
   // the first chunk of a wave's next tile is requested before the current tile's epilogue, so the wave
   // always has loads in flight (the epilogue would otherwise be a bubble in its share of the stream)
   C aA, aB;
+  typename C::Pipe pipe;
   // a tile is kb * C::kTileBytesPerKb bytes; the lane's pointer into it is offset by lane * C::kLaneBytes
   const int64_t tbytes = p.kb * C::kTileBytesPerKb;
   const int soff = C::kScaleOffset(lane);
@@ -834,6 +878,7 @@ __device__ __forceinline__ void scan_body(const ScanParams &p, const char *image
   if (wglobal < p.n_tiles) {
     const char *x0 = xlane + (p.tile0 + wglobal * p.tile_stride) * tbytes;
     aA.template load<STREAM>(x0, x0 + soff);
+    C::prime(pipe, aA);
   }
   for (int64_t i = wglobal; i < p.n_tiles; i += wtotal) {
     const int64_t tile = p.tile0 + i * p.tile_stride;
@@ -853,10 +898,10 @@ __device__ __forceinline__ void scan_body(const ScanParams &p, const char *image
       aB.template load<STREAM>(xa + C::chunk_off(c + 1), sa + C::scale_off(c + 1));
       __builtin_amdgcn_sched_barrier(0);
       const bool in = c + 2 < nch;
-      aA.template mfma_refill<STREAM>(in ? xa + C::chunk_off(c + 2) : xn, in ? sa + C::scale_off(c + 2) : sn, ldsq0, ldsq1,
-                                      c * CH, acc0, acc1);
+      aA.template mfma_refill<STREAM>(pipe, aB, in ? xa + C::chunk_off(c + 2) : xn, in ? sa + C::scale_off(c + 2) : sn, ldsq0,
+                                      ldsq1, c * CH, acc0, acc1);
       __builtin_amdgcn_sched_barrier(0);
-      aB.mfma(ldsq0, ldsq1, (c + 1) * CH, acc0, acc1);
+      aB.mfma(pipe, aA, ldsq0, ldsq1, (c + 1) * CH, acc0, acc1);
     }
 
     const int64_t row_base = tile * kTileRows + 4 * half;
@@ -940,11 +985,12 @@ template <bool DENSE, int CH, int NT, bool STREAM>
 __global__ __launch_bounds__(NT) ANR_SCAN_ATTR void k_scan8(ScanParams p) {
   scan_body<DENSE, CH, ScanChunk8<CH>, STREAM>(p, reinterpret_cast<const char *>(p.x8));
 }
-#if defined(ANR_SCAN8_AB)  // developer A/B build: the same scan with the other cache policy for the scale words, launched
-// instead of k_scan8 while the environment variable ANR_SCAN8_AB is set to 1 (tools/scan8_policy_ab.py)
-template <bool DENSE, int CH, int NT, bool STREAM>
+#if defined(ANR_SCAN8_AB)  // developer A/B build: the same scan in another form, launched instead of k_scan8 while the
+// environment variable ANR_SCAN8_AB names it: 1 the other cache policy for the scale words (tools/scan8_policy_ab.py), 2 ... the
+// arm sets of launch_scan's table (tools/scan8_arms_ab.py)
+template <bool DENSE, int CH, int NT, bool STREAM, bool SNT, int ARMS>
 __global__ __launch_bounds__(NT) ANR_SCAN_ATTR void k_scan8_ab(ScanParams p) {
-  scan_body<DENSE, CH, ScanChunk8<CH, !kScan8ScalesNT>, STREAM>(p, reinterpret_cast<const char *>(p.x8));
+  scan_body<DENSE, CH, ScanChunk8<CH, SNT, ARMS>, STREAM>(p, reinterpret_cast<const char *>(p.x8));
 }
 #endif
 
