@@ -11,3 +11,5 @@ from . import graph_quality  # noqa: F401
 from .graph_quality import compute_metrics  # noqa: F401
 from . import note_relations  # noqa: F401
 from .note_relations import SetJoin, entity_coexistence_relations, topic_relations  # noqa: F401
+from . import related_notes  # noqa: F401
+from .related_notes import NoteSimilarityCalculator, related_pairs  # noqa: F401

@@ -38,6 +38,7 @@ ANR_EEMPTY = -6
 NOTEGRAPH_OPT_MAX_SLOTS = 1
 NOTEGRAPH_OPT_BFS_WORDS = 2
 SETJOIN_OPT_TABLE_SLOTS = 1
+RELATED_OPT_PAIR_CAP = 1
 
 
 class AnoragError(RuntimeError):
@@ -88,6 +89,12 @@ class FuseDenseStats(C.Structure):
 class DiversityParams(C.Structure):
     _fields_ = [("max_candidates", C.c_int32), ("dedup", C.c_int32), ("quota", C.c_int32), ("reserved", C.c_int32),
                 ("similarity_threshold", C.c_double), ("balance_factor", C.c_double), ("quotas", C.c_int32 * 32)]
+
+
+class RelatedParams(C.Structure):
+    _fields_ = [("threshold", C.c_double), ("entity_weight", C.c_double), ("cluster_bonus", C.c_double),
+                ("min_shared", C.c_int32), ("exclude_same_cluster", C.c_int32), ("max_related", C.c_int32),
+                ("reserved", C.c_int32)]
 
 
 class EncoderConfig(C.Structure):
@@ -281,6 +288,11 @@ SIGNATURES = {
                                             C.c_void_p]),
     "anr_setjoin_pair_counts": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "anr_setjoin_set_option": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64]),
+    "anr_index_related_notes": (C.c_int, [C.c_void_p, C.POINTER(RelatedParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+    "anr_related_set_option": (C.c_int, [C.c_int32, C.c_int64]),
+    "anr_related_timing": (C.c_int, [C.c_int32, C.c_void_p]),
 }
 
 _lib = None

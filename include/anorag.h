@@ -819,6 +819,61 @@ int anr_setjoin_pair_counts(anr_setjoin *h, int64_t n, const int32_t *I, const i
 #define ANR_SETJOIN_OPT_TABLE_SLOTS 1
 int anr_setjoin_set_option(anr_setjoin *h, int32_t option, int64_t value);
 
+/* ------------------------------------------------------------------------------------------------
+ * Related notes (opt-in): NoteSimilarityCalculator.find_related_notes (utils/note_similarity.py:115-233) on the stored
+ * rows of a normalising inner-product index — the N x N cosine_similarity matrix of :144 and the double loop of
+ * _find_related_for_note (:169-233) with _calculate_entity_similarity (:235-259), without the matrix and without the
+ * loop.  DESIGN.md §5m has the semantics, the error band and the strip passes.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct anr_related_params {
+  double threshold;              /* similarity_threshold: a pair is kept when combined > threshold (strict, :210) */
+  double entity_weight;          /* entity_similarity_weight w */
+  double cluster_bonus;          /* cluster_similarity_bonus */
+  int32_t min_shared;            /* min_shared_entities */
+  int32_t exclude_same_cluster;  /* 0 / 1 */
+  int32_t max_related;           /* max_related_notes M, 1 .. 64 */
+  int32_t reserved;
+} anr_related_params;
+/* Replaces utils/note_similarity.py:142-144 and :174-221 for all rows at once.  For rows i != j:
+ *   base     = the float64 dot product of the two stored float32 rows: the products exact, added per lane l = k mod 8 in
+ *              ascending k, the eight sums joined as ((0+4)+(2+6)) + ((1+5)+(3+7)); no fused multiply-add.  The value depends
+ *              on the two rows alone: equal stored rows give bit-equal values against any third row (:191);
+ *   ent      = 0.5 if both entity rows are empty, 0.0 if one is, else min(inter / uni + (inter >= min_shared ? 0.1 : 0), 1.0)
+ *              in float64 from the two integers (:235-259);
+ *   cb       = cluster_bonus iff !exclude_same_cluster && c_i != c_j && base > threshold - 0.1, else 0 (:197-201);
+ *   combined = base * (1 - w) + ent * w + cb, left to right in float64 (:204-208);
+ *   skipped when exclude_same_cluster && c_i == c_j && c_i != -1 (:187); kept when combined > threshold (:210).
+ * Row i receives its first M kept pairs by (combined descending, column ascending) — the reference's stable
+ * sort(reverse = True) over ascending columns (:219-221).  Pairs are nominated by an MFMA walk of the f16 image with the
+ * image's error band subtracted from the smallest base that can still pass, so no passing pair is lost; every value is
+ * then taken from the float32 rows.  No floating-point atomics: the result does not depend on the order in which pairs
+ * were found, nor on the pair capacity, and two calls are bit-equal.
+ * cluster: int32 [ntotal] codes compared by equality, -1 = no cluster; NULL = all -1.  ent_indptr int64 [ntotal + 1] from 0,
+ * ent_ids int32 STRICTLY ASCENDING and >= 0 inside a row (note_relations.encode_rows).
+ * Outputs (host): nbr int32 [ntotal][M] (unused slots -1), n_nbr int32 [ntotal]; combined / base float64 and inter / uni
+ * int32 [ntotal][M] (unused slots 0; each of the four may be NULL).
+ * stats8 (may be NULL), int64 [8]: 0 pairs nominated by all walks (those of a strip that had to be cut again included),
+ * 1 pairs scored, 2 pairs kept (i < j), 3 strips, 4 pair capacity, 5 nominated pairs the f16 image could not decide
+ * (inside the band), 6 device scratch bytes of the call, 7 zero.
+ * ANR_EINVAL: an L2 index, an inner-product index without normalisation, M outside [1, 64], a NaN parameter, an entity row
+ * that descends or repeats an id, a negative id, ent_indptr not ascending from 0, ntotal >= 2^31 - 1.  ANR_ESTATE: a stored
+ * value is outside the f16 range.  ntotal == 0: ANR_OK, nothing written. */
+int anr_index_related_notes(anr_index *h, const anr_related_params *p, const int32_t *cluster, const int64_t *ent_indptr,
+                            const int32_t *ent_ids, int32_t *nbr, int32_t *n_nbr, double *combined, double *base,
+                            int32_t *inter, int32_t *uni, int64_t *stats8);
+/* option 1 = ANR_RELATED_OPT_PAIR_CAP — the pairs one walk of anr_index_related_notes may nominate (process-wide; 0 = the
+ * default: 64 pairs a row, within a quarter of the free device memory).  A walk that would nominate more is cut into strips of rows, each strip
+ * walked, scored and merged into the per-row top M kept so far; the capacity is never below ntotal, the most one row can
+ * nominate.  Tests force a small one to walk the strips on small inputs.  Results never depend on it.  Replaces nothing of
+ * the reference: utils/note_similarity.py:144 holds the whole matrix. */
+#define ANR_RELATED_OPT_PAIR_CAP 1
+int anr_related_set_option(int32_t option, int64_t value);
+/* Developer timing of anr_index_related_notes (tools/related_perf.py; process-wide, not for concurrent callers; the
+ * reference has no counterpart, its loop is utils/note_similarity.py:182-216): enable != 0 makes later calls record HIP
+ * events; ms3 (may be NULL) receives the last timed call's milliseconds summed over its strips: [0] the nominating walks,
+ * [1] pair scoring, [2] sort and per-row selection. */
+int anr_related_timing(int32_t enable, float *ms3);
+
 #ifdef __cplusplus
 }
 #endif
