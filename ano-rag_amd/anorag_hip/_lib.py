@@ -32,6 +32,7 @@ OPT_SHADOW = 11
 OPT_SCHEDULE = 12
 OPT_STREAM_WAIT = 13
 OPT_SCAN_BITS = 14
+OPT_EDIT_CHUNK_ROWS = 15
 BATCH_LOG_FIELDS = 14
 ANR_ENOCONV = -5
 ANR_EEMPTY = -6
@@ -125,6 +126,8 @@ SIGNATURES = {
     "anr_index_ntotal": (C.c_int64, [C.c_void_p]),
     "anr_index_dim": (C.c_int32, [C.c_void_p]),
     "anr_index_reset": (C.c_int, [C.c_void_p]),
+    "anr_index_remove": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "anr_index_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "anr_index_reconstruct": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     "anr_index_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     "anr_index_search_devq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),

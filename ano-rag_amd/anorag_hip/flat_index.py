@@ -131,6 +131,23 @@ class FlatIndex:
     def reset(self) -> None:
         _lib.check(self._lib.anr_index_reset(self._h), "anr_index_reset")
 
+    def remove_rows(self, rows) -> int:
+        """drop stored rows in place on the device (``faiss.IndexFlat.remove_ids``: duplicates and rows outside
+        [0, ntotal) are ignored, survivors keep their order and are renumbered densely); returns how many rows went"""
+        rows = np.ascontiguousarray(np.asarray(rows).reshape(-1), dtype=np.int64)
+        n = C.c_int64(0)
+        _lib.check(self._lib.anr_index_remove(self._h, rows.ctypes.data, rows.shape[0], C.byref(n)), "anr_index_remove")
+        return int(n.value)
+
+    def update_rows(self, rows, x) -> None:
+        """replace stored rows in place: row rows[i] becomes what ``add`` would have stored for x[i] (of a row listed more
+        than once the last entry wins; a row outside [0, ntotal) raises and changes nothing)"""
+        rows = np.ascontiguousarray(np.asarray(rows).reshape(-1), dtype=np.int64)
+        x = _f32_matrix(x, self.d, "update_rows")
+        if x.shape[0] != rows.shape[0]:
+            raise ValueError(f"update_rows: {rows.shape[0]} rows but {x.shape[0]} vectors")
+        _lib.check(self._lib.anr_index_update(self._h, rows.ctypes.data, x.ctypes.data, rows.shape[0]), "anr_index_update")
+
     def reconstruct_n(self, i0: int, n: int):
         out = np.empty((n, self.d), dtype=np.float32)
         _lib.check(self._lib.anr_index_reconstruct(self._h, int(i0), int(n), out.ctypes.data),

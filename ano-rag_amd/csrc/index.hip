@@ -23,6 +23,7 @@
 #include "common.hpp"
 #include "graph.hpp"
 #include "index_kernels.hpp"
+#include "index_edit_kernels.hpp"
 #include "tiny_kernels.hpp"
 
 using namespace anr;
@@ -121,6 +122,7 @@ struct anr_index {
   int overfetch_boost = 1;  // adaptive multiplier of the automatic K' (adapt_overfetch)
   int clean_batches = 0;
   int n_streams = kWorkspaces;  // streams the batches rotate over (1 = strictly one batch after the other)
+  int64_t edit_chunk_rows = 0;  // ANR_OPT_EDIT_CHUNK_ROWS: rows per compaction chunk of anr_index_remove (0 = from kEditStageBytes)
 
   Workspace ws[kWorkspaces];
   bool ws_ready = false;
@@ -1487,13 +1489,12 @@ int search_impl(anr_index *h, const float *q, bool q_on_host, int64_t nq, int32_
   return ANR_OK;
 }
 
-int add_impl(anr_index *h, const float *x_dev, int64_t n, hipStream_t st) {
-  ANR_TRY(grow_storage(h, h->ntotal + n));
-  ANR_TRY(drain(h));
+// k_add over rows [row0, row0 + n) of every array the index keeps (an append, or the rewrite of stored rows)
+int launch_add(anr_index *h, const float *x_dev, int64_t n, int64_t row0, hipStream_t st) {
   AddParams ap{};
   ap.xin = x_dev;
   ap.n = n;
-  ap.row0 = h->ntotal;
+  ap.row0 = row0;
   ap.dim = h->dim;
   ap.dimp = h->dimp;
   ap.kb = h->kb;
@@ -1504,14 +1505,169 @@ int add_impl(anr_index *h, const float *x_dev, int64_t n, hipStream_t st) {
   ap.stat = h->xstat;
   ap.x12 = h->x12;  // (kept up to date whenever they exist)
   ap.x8 = h->x8;
-  const int64_t t0 = h->ntotal / kTileRows, t1 = ceil_div(h->ntotal + n, kTileRows);
+  const int64_t t0 = row0 / kTileRows, t1 = ceil_div(row0 + n, kTileRows);
   hipLaunchKernelGGL(k_add, dim3((unsigned)(t1 - t0)), dim3(256), 0, st, ap);
   ANR_HIP(hipGetLastError());
+  return ANR_OK;
+}
+
+int add_impl(anr_index *h, const float *x_dev, int64_t n, hipStream_t st) {
+  ANR_TRY(grow_storage(h, h->ntotal + n));
+  ANR_TRY(drain(h));
+  ANR_TRY(launch_add(h, x_dev, n, h->ntotal, st));
   h->ntotal += n;
   h->xstat_dirty = true;
   h->x12_no_memory = false;
   graph_mark_stale(h->graph);
   return ANR_OK;
+}
+
+// the empty index, options kept (anr_index_reset; anr_index_remove of every row); the caller holds the lock
+int reset_impl(anr_index *h) {
+  ANR_TRY(drain(h));
+  ANR_HIP(hipStreamSynchronize(h->stream));
+  if (h->x16) ANR_HIP(hipMemset(h->x16, 0, (size_t)h->cap * h->dimp * sizeof(_Float16)));
+  if (h->x12) ANR_HIP(hipMemset(h->x12, 0, (size_t)h->cap * h->dimp * 3 / 2));
+  if (h->x8) ANR_HIP(hipMemset(h->x8, 0, (size_t)x8_bytes(h)));
+  if (h->rowbias) ANR_HIP(hipMemset(h->rowbias, 0, (size_t)h->cap * sizeof(float)));
+  ANR_HIP(hipMemset(h->xstat, 0, 5 * sizeof(unsigned)));
+  ANR_HIP(hipStreamSynchronize(nullptr));  // the fills run on the NULL stream; later adds use the handle's own
+  h->ntotal = 0;
+  h->xstat_dirty = true;
+  graph_mark_stale(h->graph);
+  h->f12_suspended = false;
+  h->f12_strikes = h->f12_level = h->f12_clean = h->f12_lowered = 0;
+  h->f12_hold = 64;
+  return ANR_OK;
+}
+
+// ---- in-place edits ------------------------------------------------------------------------------------
+constexpr int64_t kEditStageBytes = 256ll << 20;  // device staging of a compaction chunk / of the host rows of an update
+
+// Zero the certificate statistics and recount them over the h->ntotal stored rows with k_reimage, which also rewrites the
+// images of tiles write_tile0 .. tiles - 1 (INT64_MAX: none).  Enqueued on h->stream.
+int launch_reimage(anr_index *h, int64_t tiles, int64_t write_tile0) {
+  ANR_HIP(hipMemsetAsync(h->xstat, 0, 5 * sizeof(unsigned), h->stream));
+  if (tiles <= 0) return ANR_OK;
+  ReimageParams rp{};
+  rp.x32 = h->x32;
+  rp.n_rows = h->ntotal;
+  rp.write_tile0 = write_tile0;
+  rp.dim = h->dim;
+  rp.dimp = h->dimp;
+  rp.kb = h->kb;
+  rp.x16 = h->x16;
+  rp.rowbias = h->rowbias;
+  rp.stat = h->xstat;
+  rp.x12 = h->x12;
+  rp.x8 = h->x8;
+  hipLaunchKernelGGL(k_reimage, dim3((unsigned)tiles), dim3(256), 0, h->stream, rp);
+  ANR_HIP(hipGetLastError());
+  return ANR_OK;
+}
+
+// one chunk of the stable compaction of `a` ([..][width]): destination rows [j0, j0 + len) take their source rows, through
+// `stage` unless the chunk's smallest shift c0 clears the chunk (then no source lies inside it)
+int compact_chunk(anr_index *h, float *a, int width, const int64_t *gm_dev, int64_t m, int64_t j0, int64_t len, int64_t c0,
+                  float *stage) {
+  const bool direct = c0 >= len;
+  GatherParams gp{a, direct ? a : stage, gm_dev, m, j0, len, direct ? j0 : 0, width};
+  const bool vec = width % 4 == 0;
+  const int64_t units = len * (vec ? width / 4 : width);
+  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(units, 256), (int64_t)h->n_cu * 16));
+  if (vec) hipLaunchKernelGGL(k_gather_rows<true>, dim3(grid), dim3(256), 0, h->stream, gp);
+  else hipLaunchKernelGGL(k_gather_rows<false>, dim3(grid), dim3(256), 0, h->stream, gp);
+  ANR_HIP(hipGetLastError());
+  if (!direct)
+    ANR_HIP(hipMemcpyAsync(a + j0 * width, stage, (size_t)len * width * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+  return ANR_OK;
+}
+
+int remove_impl(anr_index *h, const int64_t *rows, int64_t n, int64_t *n_removed) {
+  ANR_TRY(drain(h));
+  std::vector<int64_t> gone;
+  for (int64_t i = 0; i < n; ++i)
+    if (rows[i] >= 0 && rows[i] < h->ntotal) gone.push_back(rows[i]);
+  std::sort(gone.begin(), gone.end());
+  gone.erase(std::unique(gone.begin(), gone.end()), gone.end());
+  const int64_t m = (int64_t)gone.size();
+  if (m == 0) return ANR_OK;
+  if (m == h->ntotal) {
+    ANR_TRY(reset_impl(h));
+    if (n_removed) *n_removed = m;
+    return ANR_OK;
+  }
+  const int64_t old_n = h->ntotal, new_n = old_n - m, r0 = gone[0];
+  std::vector<int64_t> gm((size_t)m);  // gone[i] - i, non-decreasing: the source map's search key (index_edit_kernels.hpp)
+  for (int64_t i = 0; i < m; ++i) gm[(size_t)i] = gone[(size_t)i] - i;
+  // every allocation before the first byte of the index changes
+  int64_t chunk = h->edit_chunk_rows > 0 ? h->edit_chunk_rows : std::max<int64_t>(kTileRows, kEditStageBytes / (h->dim * 4));
+  chunk = std::max<int64_t>(1, std::min(chunk, new_n - r0));
+  int64_t *gm_dev = nullptr;
+  float *stage = nullptr;
+  int rc = dev_alloc(&gm_dev, m, false);
+  if (rc == ANR_OK && new_n > r0) rc = dev_alloc(&stage, chunk * h->dim, false);
+  if (rc == ANR_OK && hipMemcpy(gm_dev, gm.data(), (size_t)m * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess)
+    rc = fail(ANR_EHIP, "uploading the removed rows failed");
+  for (int64_t j0 = r0; j0 < new_n && rc == ANR_OK; j0 += chunk) {
+    const int64_t len = std::min(chunk, new_n - j0);
+    const int64_t c0 = std::upper_bound(gm.begin(), gm.end(), j0) - gm.begin();
+    rc = compact_chunk(h, h->x32, h->dim, gm_dev, m, j0, len, c0, stage);
+    if (rc == ANR_OK && h->rowbias) rc = compact_chunk(h, h->rowbias, 1, gm_dev, m, j0, len, c0, stage);
+  }
+  if (rc == ANR_OK) {
+    h->ntotal = new_n;
+    rc = launch_reimage(h, ceil_div(old_n, kTileRows), r0 / kTileRows);
+  }
+  if (hipStreamSynchronize(h->stream) != hipSuccess && rc == ANR_OK) rc = fail(ANR_EHIP, "the removal's kernels failed");
+  dev_free(gm_dev);
+  dev_free(stage);
+  h->xstat_dirty = true;
+  graph_mark_stale(h->graph);
+  if (rc == ANR_OK && n_removed) *n_removed = m;
+  return rc;
+}
+
+int update_impl(anr_index *h, const int64_t *rows, const float *x_host, int64_t n) {
+  for (int64_t i = 0; i < n; ++i)
+    if (rows[i] < 0 || rows[i] >= h->ntotal)
+      return fail(ANR_EINVAL, "row %lld is outside the index (0..%lld)", (long long)rows[i], (long long)h->ntotal - 1);
+  ANR_TRY(drain(h));
+  // (row, position in x_host), ascending by row; of a row listed more than once the last entry stays
+  std::vector<std::pair<int64_t, int64_t>> ord((size_t)n);
+  for (int64_t i = 0; i < n; ++i) ord[(size_t)i] = {rows[i], i};
+  std::sort(ord.begin(), ord.end());
+  size_t u = 0;
+  for (size_t i = 0; i < ord.size(); ++i)
+    if (i + 1 == ord.size() || ord[i + 1].first != ord[i].first) ord[u++] = ord[i];
+  ord.resize(u);
+  // the host rows go through a bounded device staging buffer, in row order; k_add rewrites each run of consecutive rows
+  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>((int64_t)u, kEditStageBytes / (h->dim * 4)));
+  float *stage = nullptr;
+  ANR_TRY(dev_alloc(&stage, chunk * h->dim, false));
+  std::vector<float> pack((size_t)chunk * h->dim);
+  int rc = ANR_OK;
+  for (int64_t i0 = 0; i0 < (int64_t)u && rc == ANR_OK; i0 += chunk) {
+    const int64_t len = std::min(chunk, (int64_t)u - i0);
+    for (int64_t i = 0; i < len; ++i)
+      std::memcpy(pack.data() + i * h->dim, x_host + ord[(size_t)(i0 + i)].second * h->dim, (size_t)h->dim * sizeof(float));
+    if (hipMemcpyAsync(stage, pack.data(), (size_t)len * h->dim * sizeof(float), hipMemcpyHostToDevice, h->stream) != hipSuccess)
+      rc = fail(ANR_EHIP, "hipMemcpyAsync failed");
+    for (int64_t a = 0; a < len && rc == ANR_OK;) {
+      int64_t b = a + 1;
+      while (b < len && ord[(size_t)(i0 + b)].first == ord[(size_t)(i0 + b - 1)].first + 1) ++b;
+      rc = launch_add(h, stage + a * h->dim, b - a, ord[(size_t)(i0 + a)].first, h->stream);
+      a = b;
+    }
+    if (hipStreamSynchronize(h->stream) != hipSuccess && rc == ANR_OK) rc = fail(ANR_EHIP, "the update's kernels failed");
+  }
+  // the replaced rows' old norms and image errors may have been the maxima: recount over every row
+  if (rc == ANR_OK) rc = launch_reimage(h, ceil_div(h->ntotal, kTileRows), INT64_MAX);
+  if (hipStreamSynchronize(h->stream) != hipSuccess && rc == ANR_OK) rc = fail(ANR_EHIP, "the update's kernels failed");
+  dev_free(stage);
+  h->xstat_dirty = true;
+  graph_mark_stale(h->graph);
+  return rc;
 }
 
 void free_workspaces(anr_index *h) {
@@ -1675,21 +1831,23 @@ int anr_index_reset(anr_index *h) {
   if (!h) return fail(ANR_EINVAL, "null handle");
   DeviceGuard g(h->device);
   std::lock_guard<std::mutex> lk(h->mu);
-  ANR_TRY(drain(h));
-  ANR_HIP(hipStreamSynchronize(h->stream));
-  if (h->x16) ANR_HIP(hipMemset(h->x16, 0, (size_t)h->cap * h->dimp * sizeof(_Float16)));
-  if (h->x12) ANR_HIP(hipMemset(h->x12, 0, (size_t)h->cap * h->dimp * 3 / 2));
-  if (h->x8) ANR_HIP(hipMemset(h->x8, 0, (size_t)x8_bytes(h)));
-  if (h->rowbias) ANR_HIP(hipMemset(h->rowbias, 0, (size_t)h->cap * sizeof(float)));
-  ANR_HIP(hipMemset(h->xstat, 0, 5 * sizeof(unsigned)));
-  ANR_HIP(hipStreamSynchronize(nullptr));  // the fills run on the NULL stream; later adds use the handle's own
-  h->ntotal = 0;
-  h->xstat_dirty = true;
-  graph_mark_stale(h->graph);
-  h->f12_suspended = false;
-  h->f12_strikes = h->f12_level = h->f12_clean = h->f12_lowered = 0;
-  h->f12_hold = 64;
-  return ANR_OK;
+  return reset_impl(h);
+}
+
+int anr_index_remove(anr_index *h, const int64_t *rows_host, int64_t n, int64_t *n_removed) {
+  if (n_removed) *n_removed = 0;
+  if (!h || (!rows_host && n > 0) || n < 0) return fail(ANR_EINVAL, "bad argument");
+  DeviceGuard g(h->device);
+  std::lock_guard<std::mutex> lk(h->mu);
+  return remove_impl(h, rows_host, n, n_removed);
+}
+
+int anr_index_update(anr_index *h, const int64_t *rows_host, const float *x_host, int64_t n) {
+  if (!h || ((!rows_host || !x_host) && n > 0) || n < 0) return fail(ANR_EINVAL, "bad argument");
+  DeviceGuard g(h->device);
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (n == 0) return drain(h);
+  return update_impl(h, rows_host, x_host, n);
 }
 
 int anr_index_reconstruct(anr_index *h, int64_t i0, int64_t n, float *out_host) {
@@ -2058,6 +2216,10 @@ int anr_index_set_option(anr_index *h, int32_t opt, int64_t value) {
       if (value != 8 && value != 0) dev_free(h->x8);
       break;
     }
+    case ANR_OPT_EDIT_CHUNK_ROWS:
+      if (value < 0) return fail(ANR_EINVAL, "edit chunk rows must be >= 0");
+      h->edit_chunk_rows = value;
+      break;
     case ANR_OPT_STREAMS:
       if (value < 1 || value > kWorkspaces) return fail(ANR_EINVAL, "streams must be in 1..%d", kWorkspaces);
       h->n_streams = (int)value;

@@ -383,6 +383,8 @@ class VectorRetriever:
             if not rows:
                 logger.warning("No matching notes found to remove")
                 return True
+            if self._inplace_edits():
+                return self._remove_rows_in_place(rows)
             for r in rows:
                 if r < len(self.atomic_notes):
                     del self.atomic_notes[r]
@@ -404,10 +406,44 @@ class VectorRetriever:
                 return False
             if self.note_embeddings is not None:
                 self.note_embeddings[row] = emb[0]
+            if self._inplace_edits():
+                if not self.vector_index.update_vectors(np.array([row], dtype=np.int64), emb[:1]):
+                    logger.error("Failed to update the vector in the index")
+                    return False
+                self._build_id_mappings()  # the note may carry another note_id
+                if self.bm25_enabled:
+                    self._build_bm25_index(self.atomic_notes)
+                return True
             return self.build_index(self.atomic_notes, force_rebuild=True)
         except Exception as e:
             logger.error(f"Failed to update note {note_id}: {e}")
             return False
+
+    # EXTENSION (not in the reference; opt-in): anorag_hip.inplace_edits
+    def _inplace_edits(self) -> bool:
+        """config key ``anorag_hip.inplace_edits`` (default false) on an exact or graph index: remove_notes / update_note
+        edit the rows on the device instead of re-encoding and re-adding every note"""
+        from anorag_hip import FlatIndex
+        return bool(config.get("anorag_hip.inplace_edits", False)) and isinstance(self.vector_index.index, FlatIndex)
+
+    def _remove_rows_in_place(self, rows: List[int]) -> bool:
+        """rows: descending rows of atomic_notes (== rows of the index, build_index adds the notes in order)"""
+        rows = [r for r in rows if r < len(self.atomic_notes)]
+        if len(rows) == len(self.atomic_notes):
+            logger.warning("No atomic notes provided for indexing")  # what the rebuild of an empty list answers
+            return False
+        if not self.vector_index.remove_vectors(np.array(rows, dtype=np.int64)):
+            logger.error("Failed to remove vectors from index")
+            return False
+        self.vector_index.renumber_ids()  # the survivors are rows 0..n-1 of atomic_notes again
+        for r in rows:
+            del self.atomic_notes[r]
+        if self.note_embeddings is not None:
+            self.note_embeddings = np.delete(self.note_embeddings, rows, axis=0)
+        self._build_id_mappings()
+        if self.bm25_enabled:
+            self._build_bm25_index(self.atomic_notes)
+        return True
 
     # -- lookups -------------------------------------------------------------------------------------
     def get_note_by_id(self, note_id: str) -> Optional[Dict[str, Any]]:

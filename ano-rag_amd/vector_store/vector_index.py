@@ -587,6 +587,14 @@ class VectorIndex:
             n = self.index.ntotal
             cur = self._ids if self._ids is not None else np.arange(n, dtype=np.int64)
             keep = ~np.isin(cur, drop)
+            if type(self.index) is FlatIndex:
+                # one device, exact index: the rows are compacted where they are (anr_index_remove), no corpus round trip
+                self.index.remove_rows(np.flatnonzero(~keep))
+                if self._ids is not None or self.index_type in ("IVFFlat", "IVFPQ"):
+                    self._ids = cur[keep]
+                self.total_vectors -= n_requested
+                logger.info(f"Removed {n_requested} vectors from index")
+                return True
             rows = self.index.reconstruct_n(0, n)[keep] if n else np.zeros((0, self.embedding_dim), np.float32)
             # build the replacement beside the live index and swap only when it is complete
             fresh = self._new_index(int(self.index.d), self.index.metric, self.index.normalize,
@@ -609,6 +617,41 @@ class VectorIndex:
         except Exception as e:
             logger.error(f"Failed to remove vectors: {e}")
             return False
+
+    def update_vectors(self, ids: np.ndarray, vectors: np.ndarray) -> bool:
+        """EXTENSION (not in the reference): replace the stored vectors of ``ids`` (the ids ``search`` returns) in place
+        on the device, preprocessed as ``add_vectors`` would have (anr_index_update).  Exact single-device and graph
+        indexes only; an unknown id, an IVF-typed or a sharded index returns False with nothing changed."""
+        if self.index is None:
+            logger.error("Index not created yet")
+            return False
+        try:
+            if not isinstance(self.index, FlatIndex):
+                raise ValueError(f"in-place update is not supported by {type(self.index).__name__}")
+            ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+            v = np.asarray(vectors)
+            if v.ndim != 2 or len(v) != len(ids):
+                raise ValueError("vectors must be 2-D with one row per id")
+            if self._ids is None:
+                rows = ids
+            else:
+                order = np.argsort(self._ids, kind="stable")
+                pos = np.searchsorted(self._ids, ids, sorter=order)
+                rows = order[np.minimum(pos, len(order) - 1)] if len(order) else np.full(len(ids), -1, np.int64)
+                rows = np.where((pos < len(order)) & (self._ids[rows] == ids), rows, -1)
+            self.index.update_rows(rows, v)  # a row outside the index raises before anything changes
+            logger.info(f"Updated {len(ids)} vectors in index")
+            return True
+        except Exception as e:
+            logger.error(f"Failed to update vectors: {e}")
+            return False
+
+    def renumber_ids(self) -> None:
+        """EXTENSION: forget the ids the rows were added under — an exact or graph index then answers with row numbers
+        0..ntotal-1 (what a fresh index of the same rows, added with sequential ids, answers).  IVF-typed real indexes
+        keep their ids (their insertion numbers are never reused)."""
+        if not self._ivf():
+            self._ids = None
 
     def _ivf_count(self) -> int:
         """rows ever added to the IVF index (its insertion numbers are 0..this-1)"""

@@ -62,6 +62,21 @@ int anr_index_add_dev(anr_index *h, const float *x_dev, int64_t n, void *stream)
 int64_t anr_index_ntotal(const anr_index *h);
 int32_t anr_index_dim(const anr_index *h);
 int anr_index_reset(anr_index *h);
+/* Edit the stored rows in place on the device (no corpus round trip; the row-major float32 rows are compacted or rewritten
+ * and every scan image and certificate statistic is re-derived from them).  `rows` are the index's own row numbers
+ * 0 .. ntotal-1 (ANR_OPT_ID_OFFSET is not applied).  Both calls retire every in-flight batch first (a batch submitted before
+ * the edit answers from the pre-edit rows), return when the device work is complete, mark a graph index on the rows stale
+ * and leave ANR_OPT_SCAN_BITS and the coarse image's K' ladder alone.  All device memory they need is allocated before the
+ * first byte changes: an allocation failure leaves the index as it was.
+ * anr_index_remove: faiss.IndexFlat.remove_ids (vector_index.py:587-608 without the rebuild) — duplicates and rows outside
+ *   [0, ntotal) are ignored, *n_removed (may be NULL) counts the distinct rows dropped, survivors keep their order and are
+ *   renumbered densely; removing every row leaves the state of anr_index_reset.  The largest norm and image errors are
+ *   recounted over the survivors, so dropping the row that held a maximum tightens the certificate again.
+ * anr_index_update: x_host[i] replaces row rows[i], preprocessed and stored bit for bit as anr_index_add would have stored
+ *   it (normalised unless ANR_OPT_ADD_RAW); any row outside [0, ntotal) -> ANR_EINVAL with nothing changed; of a row listed
+ *   more than once the last entry wins. */
+int anr_index_remove(anr_index *h, const int64_t *rows_host, int64_t n, int64_t *n_removed);
+int anr_index_update(anr_index *h, const int64_t *rows_host, const float *x_host, int64_t n);
 /* copy the stored (already preprocessed) float32 rows [i0, i0+n) back to the host */
 int anr_index_reconstruct(anr_index *h, int64_t i0, int64_t n, float *out_host);
 
@@ -324,6 +339,9 @@ int anr_index_set_option(anr_index *h, int32_t opt, int64_t value);
                                      codes with one f16 scale per row and 32 dimensions (1.0625 bytes per value, its own K'
                                      ladder from 320 at k = 100); 0 picks it from 2 097 152 rows on.  Only the image in use is
                                      built (with 0, the first search that wants it builds it) */
+
+#define ANR_OPT_EDIT_CHUNK_ROWS 15 /* destination rows anr_index_remove compacts per step (gather into a staging buffer, write back);
+                                     0 (default) = as many as a 256 MiB staging buffer holds.  Identical results for any value */
 
 typedef struct anr_search_stats {
   int64_t n_queries;        /* queries of the last search call                                        */
