@@ -13,3 +13,6 @@ from . import note_relations  # noqa: F401
 from .note_relations import SetJoin, entity_coexistence_relations, topic_relations  # noqa: F401
 from . import related_notes  # noqa: F401
 from .related_notes import NoteSimilarityCalculator, related_pairs  # noqa: F401
+from . import note_dedup  # noqa: F401
+from .note_dedup import TfidfJoin, detect_duplicate_notes, entity_duplicates, lexical_duplicates  # noqa: F401
+from .note_dedup import relabel_terms, semantic_duplicates  # noqa: F401

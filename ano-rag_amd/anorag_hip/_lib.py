@@ -40,6 +40,7 @@ NOTEGRAPH_OPT_MAX_SLOTS = 1
 NOTEGRAPH_OPT_BFS_WORDS = 2
 SETJOIN_OPT_TABLE_SLOTS = 1
 RELATED_OPT_PAIR_CAP = 1
+TFIDF_OPT_TABLE_SLOTS = 1
 
 
 class AnoragError(RuntimeError):
@@ -296,6 +297,13 @@ SIGNATURES = {
                                           C.c_void_p]),
     "anr_related_set_option": (C.c_int, [C.c_int32, C.c_int64]),
     "anr_related_timing": (C.c_int, [C.c_int32, C.c_void_p]),
+    "anr_tfidf_create": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.POINTER(C.c_void_p)]),
+    "anr_tfidf_destroy": (C.c_int, [C.c_void_p]),
+    "anr_tfidf_self_join": (C.c_int, [C.c_void_p, C.c_double, C.POINTER(C.c_int64), C.c_void_p]),
+    "anr_tfidf_self_join_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "anr_tfidf_scores": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "anr_tfidf_set_option": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64]),
 }
 
 _lib = None

@@ -16,4 +16,13 @@ constexpr int sj_table_fill(int slots) { return slots - slots / 4; }
 // the table's keys and counts, the compaction buffer (16 bytes a slot), 256 partial sums and the pass's counters
 constexpr int sj_lds_bytes(int slots) { return slots * 16 + kSjThreads * 4 + 32; }
 
+#if defined(__HIPCC__)
+// the kernels of setjoin.hip that turn a CSR into postings around the one radix sort, and the one-workgroup exclusive
+// scan of per-row counts (out[n] = the total); tfidf.hip launches them too
+__global__ void k_sj_keys(const int64_t *indptr, const int32_t *items, int64_t n_rows, int64_t nnz, unsigned long long *keys);
+__global__ void k_sj_post_ptr(const unsigned long long *sorted, int64_t nnz, int64_t n_items, int64_t *post_ptr);
+__global__ void k_sj_post_rows(const unsigned long long *sorted, int64_t nnz, int32_t *post_rows);
+__global__ void k_sj_scan(const int64_t *in, int64_t n, int64_t *out);
+#endif
+
 }  // namespace anr

@@ -86,6 +86,7 @@ class VectorRetriever:
         self.tfidf_vectorizer = None
         self.tfidf_matrix = None
         self.processed_texts: List[str] = []
+        self.tfidf_join = None  # EXTENSION (opt-in, anorag_hip.tfidf_device): the matrix on the device, see _bm25_search
 
         self.hybrid_searcher = None
         self.hybrid_config = config.get("vector_store.hybrid_search", {}) or {}
@@ -557,8 +558,15 @@ class VectorRetriever:
         self.index_to_note_id = {}
         if self.vector_index:
             self.vector_index.reset_index()
+        self._close_tfidf_join()
+
+    def _close_tfidf_join(self):
+        join, self.tfidf_join = getattr(self, "tfidf_join", None), None
+        if join is not None:
+            join.close()
 
     def cleanup(self):
+        self._close_tfidf_join()
         if self.embedding_manager:
             self.embedding_manager.cleanup()
         if self.vector_index:
@@ -603,6 +611,12 @@ class VectorRetriever:
                                                     ngram_range=(1, 2))
             if texts:
                 self.tfidf_matrix = self.tfidf_vectorizer.fit_transform(texts)
+            self._close_tfidf_join()
+            # anorag_hip.tfidf_device (default false): _bm25_search takes its similarities from the device
+            # (anorag_hip.TfidfJoin.scores, csrc/tfidf.hip; bit-equal to cosine_similarity)
+            if self.tfidf_matrix is not None and bool(config.get("anorag_hip.tfidf_device", False)):
+                from anorag_hip.note_dedup import TfidfJoin
+                self.tfidf_join = TfidfJoin(self.tfidf_matrix, int(config.get("anorag_hip.device", 0) or 0))
         except Exception as e:
             logger.error(f"Failed to build BM25 index: {e}")
             self.bm25_enabled = False
@@ -615,9 +629,12 @@ class VectorRetriever:
         if not self.bm25_enabled or not self.tfidf_vectorizer or self.tfidf_matrix is None:
             return []
         try:
-            from sklearn.metrics.pairwise import cosine_similarity
             qv = self.tfidf_vectorizer.transform([self._preprocess_text(query)])
-            sims = cosine_similarity(qv, self.tfidf_matrix).flatten()
+            if getattr(self, "tfidf_join", None) is not None:
+                sims = self.tfidf_join.scores(qv).flatten()
+            else:
+                from sklearn.metrics.pairwise import cosine_similarity
+                sims = cosine_similarity(qv, self.tfidf_matrix).flatten()
             out = []
             for row in np.argsort(sims)[::-1][:top_k]:
                 if row < len(self.atomic_notes) and sims[row] > 0:

@@ -892,6 +892,44 @@ int anr_related_set_option(int32_t option, int64_t value);
  * [1] pair scoring, [2] sort and per-row selection. */
 int anr_related_timing(int32_t enable, float *ms3);
 
+/* ------------------------------------------------------------------------------------------------
+ * TF-IDF cosine join and search (opt-in): the N x N cosine_similarity matrix and the i < j loop of
+ * NoteValidator._find_semantic_duplicates (utils/note_validator.py:363-393) without the matrix and without the loop, and
+ * the per-document sums of VectorRetriever._bm25_search (vector_store/retriever.py:966-1002).  A handle holds one sparse
+ * float64 matrix on one device: rows are notes, items are term labels.  Every value is a sum of products, one rounded
+ * multiply and one rounded add each, in ascending label order: with the labels of anorag_hip.note_dedup.relabel_terms that
+ * is sklearn's own value, bit for bit.  DESIGN.md §5o and the top of csrc/tfidf.hip.  Calls on one handle are serialised.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct anr_tfidf anr_tfidf;
+/* Row r holds terms[indptr[r] .. indptr[r+1]) with values[...] beside them, labels STRICTLY ASCENDING in [0, n_terms).
+ * ANR_EINVAL, before any device work, for a row that descends or repeats a label, a label out of range, a value that is not
+ * finite or is negative, a row whose sum of squares exceeds 1 + 2^-20 (pass rows of unit length; all-zero and empty rows
+ * are legal), and the size limits of anr_setjoin_create. */
+int anr_tfidf_create(int32_t device, int64_t n_rows, int64_t n_terms, const int64_t *indptr, const int32_t *terms,
+                     const double *values, anr_tfidf **out);
+int anr_tfidf_destroy(anr_tfidf *h);
+/* Every pair i < j whose dot product s = (((0.0 + x_i0 * x_j0) + x_i1 * x_j1) + ...) over the shared labels ascending, in
+ * float64 without fused multiply-add, is >= threshold.  threshold <= 0, NaN and > 2 are ANR_EINVAL: a pair that shares no
+ * term is never looked at.  Pairs are nominated by an integer upper bound of 2^30 * s that cannot miss a passing pair and
+ * decided by the exact value; two calls are bit-equal.  The result stays on the handle until the next call; *n_pairs (may be
+ * NULL) = the pairs kept.  A nominated set that does not fit in the device's free memory is ANR_EHIP, never a truncation.
+ * stats8 (may be NULL), int64 [8]: 0 rows that had candidates, 1 candidate insertions into the table, 2 pairs nominated,
+ * 3 pairs kept, 4 rows_overflowed (more than one pass of the table), 5 table slots, 6 microseconds of the nominating stage
+ * and 7 of the deciding stage (HIP events on the handle's stream). */
+int anr_tfidf_self_join(anr_tfidf *h, double threshold, int64_t *n_pairs, int64_t *stats8);
+/* the pairs sorted by (i, j), the order of the reference's loop (:382-386), with their values.  ANR_ESTATE before a join. */
+int anr_tfidf_self_join_fetch(anr_tfidf *h, int32_t *I /*[n_pairs]*/, int32_t *J, double *sim);
+/* cosine_similarity(q, M) of retriever.py:983 for nq queries: out_host float64 [nq][n_rows], per document
+ * 0.0 + q_weights[0] * m + q_weights[1] * m + ... over the terms of query q in the order given, one addition at a time;
+ * a document none of the terms occurs in stays 0.0.  nq == 0 and a query with no terms are legal.  ANR_EINVAL for a label
+ * outside [0, n_terms), a weight that is not finite, q_indptr not ascending from 0, nq * n_rows above 2^37. */
+int anr_tfidf_scores(anr_tfidf *h, int64_t nq, const int64_t *q_indptr, const int32_t *q_terms, const double *q_weights,
+                     double *out_host);
+/* option 1 = ANR_TFIDF_OPT_TABLE_SLOTS: as ANR_SETJOIN_OPT_TABLE_SLOTS (a power of two in [64, 4096], 0 = the default);
+ * results never depend on it. */
+#define ANR_TFIDF_OPT_TABLE_SLOTS 1
+int anr_tfidf_set_option(anr_tfidf *h, int32_t option, int64_t value);
+
 #ifdef __cplusplus
 }
 #endif
