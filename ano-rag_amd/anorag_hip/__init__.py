@@ -16,3 +16,5 @@ from .related_notes import NoteSimilarityCalculator, related_pairs  # noqa: F401
 from . import note_dedup  # noqa: F401
 from .note_dedup import TfidfJoin, detect_duplicate_notes, entity_duplicates, lexical_duplicates  # noqa: F401
 from .note_dedup import relabel_terms, semantic_duplicates  # noqa: F401
+from . import khop_rerank  # noqa: F401
+from .khop_rerank import cluster_suppression, rerank_khop  # noqa: F401

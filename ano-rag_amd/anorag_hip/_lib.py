@@ -93,6 +93,11 @@ class DiversityParams(C.Structure):
                 ("similarity_threshold", C.c_double), ("balance_factor", C.c_double), ("quotas", C.c_int32 * 32)]
 
 
+class KhopParams(C.Structure):
+    _fields_ = [("dense_w", C.c_double), ("bm25_w", C.c_double), ("focused_w2", C.c_double), ("cov_w", C.c_double),
+                ("cons_w", C.c_double), ("rrf_lambda", C.c_double), ("rrf_k", C.c_double)]
+
+
 class RelatedParams(C.Structure):
     _fields_ = [("threshold", C.c_double), ("entity_weight", C.c_double), ("cluster_bonus", C.c_double),
                 ("min_shared", C.c_int32), ("exclude_same_cluster", C.c_int32), ("max_related", C.c_int32),
@@ -154,6 +159,11 @@ SIGNATURES = {
     "anr_index_diversify": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "anr_diversify_timing": (C.c_int, [C.c_int32, C.c_void_p]),
+    "anr_index_khop_rerank": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64] + [C.c_void_p] * 14 + [C.POINTER(KhopParams)]
+                              + [C.c_void_p] * 4),
+    "anr_index_cluster_suppress": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_void_p]),
+    "anr_khop_timing": (C.c_int, [C.c_int32, C.c_void_p]),
     "anr_index_cluster_quality": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "anr_cluster_quality_timing": (C.c_int, [C.c_int32, C.c_void_p]),

@@ -1,6 +1,6 @@
 // What the side files need of the flat index in index.hip.  graph.hip (the anr_index_graph_* entry points): the graph
 // lives on the anr_index handle and reads its stored float32 rows; it keeps no copy of the corpus.  diversity.hip,
-// cluster_quality.hip, kmeans.hip and cluster.hip: the same rows (IndexCore), and for the first three the arenas they keep
+// cluster_quality.hip, kmeans.hip, khop.hip and cluster.hip: the same rows (IndexCore), and for the first four the arenas they keep
 // on the handle between calls (IndexScratch).
 #pragma once
 #include <mutex>
@@ -26,6 +26,8 @@ struct IndexScratch {
   DevBuf<unsigned char> div_arena;  // ... every small input and output array of one call
   DevBuf<unsigned char> cq_arena;   // anr_index_cluster_quality: every array of one call
   DevBuf<unsigned char> km_arena;   // anr_index_kmeans: every array of one call
+  DevBuf<unsigned char> khop_sim;   // anr_index_cluster_suppress: the per-query Gram matrices, float64
+  DevBuf<unsigned char> khop_arena; // anr_index_khop_rerank, anr_index_cluster_suppress: every small array of one call
 };
 
 IndexCore index_core(anr_index *h);     // index.hip

@@ -49,6 +49,46 @@ def _text_of(content) -> str:
     return content if isinstance(content, str) else str(content)
 
 
+def _float_or(d, key, default):
+    try:
+        return float(d.get(key, default))
+    except (TypeError, ValueError):
+        return default
+
+
+def _khop_config():
+    """weights and suppression settings of the second hop as the reference reads them (query_processor.py:1554-1583,
+    :1643-1659): its defaults, and the default again where a value cannot be parsed"""
+    fus = config.get("hybrid_search.fusion", {}) or {}
+    feat = config.get("hybrid_search.features", {}) or {}
+    cs = config.get("hybrid_search.cluster_suppression", {}) or {}
+    w = {"dense_weight": _float_or(fus, "dense_weight", 1.0), "bm25_weight": _float_or(fus, "bm25_weight", 0.6),
+         "focused_weight_hop2": _float_or(fus, "focused_weight_hop2", 0.30), "rrf_lambda": _float_or(fus, "rrf_lambda", 0.2),
+         "hop_decay": _float_or(feat, "hop_decay", 0.85), "cov_weight": _float_or(feat, "cov_weight", 0.10),
+         "cons_weight": _float_or(feat, "cons_weight", 0.05)}
+    enabled = cs.get("enabled", True)
+    if isinstance(enabled, str):
+        enabled = enabled.strip().lower() not in {"false", "0", "no"}
+    else:
+        enabled = bool(enabled)
+    try:
+        keep_m = int(cs.get("keep_per_cluster", 2))
+    except (TypeError, ValueError):
+        keep_m = 2
+    return w, enabled, _float_or(cs, "cos_threshold", 0.90), keep_m
+
+
+def _cov_cons(note, path_entities):
+    """entity coverage and path consistency of a candidate, the reference's host expression (query_processor.py:843-852)"""
+    ne = set(note.get("entities") or [])
+    pe = set(e.lower() for e in (path_entities or []))
+    if not pe:
+        return 0.0, 0
+    cov = len({e.lower() for e in ne} & pe) / max(1, len(pe))
+    text = f"{note.get('title', '')} {note.get('content', '')}".lower()
+    return float(cov), int(1 if any(e in text for e in pe) else 0)
+
+
 class VectorRetriever:
     """Vector retriever: embedding manager + vector index + the notes (reference retriever.py:29)."""
 
@@ -352,6 +392,54 @@ class VectorRetriever:
         sims = self.vector_index.index.score_rows(q_emb, ids)
         return [[0.0 if (ids[i, j] < 0 or not np.isfinite(sims[i, j])) else max(0.0, float(sims[i, j]))
                  for j in range(len(cand))] for i, cand in enumerate(candidates)]
+
+    def rerank_second_hop(self, query: str, candidates: List[Dict[str, Any]], q_focus: Optional[str] = None,
+                          path_entities: Optional[List[str]] = None, bm25_scores: Optional[List[float]] = None,
+                          suppress: bool = True) -> List[Dict[str, Any]]:
+        """EXTENSION (not in the reference; opt-in): the second hop's rerank and cluster suppression
+        (query_processor.py:1549-1697) for one query, from the embeddings already on the device — one encoder forward for
+        ``query`` and ``q_focus`` instead of one per candidate (:1586, :1616), and the stored rows where the reference
+        calls the non-existent ``vector_index.embed``.  Not wired into any reference call path:
+        stored embeddings instead of re-encoded text change the scores.  ``candidates`` are note dicts (``note_id``,
+        ``hop_no``, ``retrieval_method``, ``similarity_score``, ``entities``, ``title``, ``content``); ``q_focus`` the
+        focus phrase the caller assembled (empty or ``None``: focused is 0.0); ``bm25_scores`` one per candidate (default
+        0.0, as the reference without a BM25 method).  Config keys and defaults are the reference's:
+        ``hybrid_search.fusion.*``, ``hybrid_search.features.*``, ``hybrid_search.cluster_suppression.*``.  Sets
+        ``final_score`` on the dicts and returns them reranked and, unless disabled, suppressed.  Raises ``ValueError``
+        for repeated or unknown note ids."""
+        from anorag_hip.khop_rerank import check_unique_note_ids, cluster_suppression, rerank_khop
+        if not candidates:
+            return []
+        index = self.vector_index.index
+        if index is None:
+            raise ValueError("rerank_second_hop needs a built index")
+        w, enabled, thr, keep_m = _khop_config()
+        ids = [c.get("note_id") for c in candidates]
+        check_unique_note_ids([ids])
+        missing = [n for n in ids if n not in self.note_id_to_index]
+        if missing:
+            raise ValueError(f"rerank_second_hop: note ids without a stored embedding: {missing[:5]}")
+        rows = [self.note_id_to_index[n] for n in ids]
+        emb = np.asarray(self.embedding_manager.encode_queries([query, q_focus] if q_focus else [query]), dtype=np.float32)
+        cc = [_cov_cons(c, path_entities) for c in candidates]
+        n = len(candidates)
+        bm25 = [float(v) for v in bm25_scores][:n] if bm25_scores is not None else []
+        bm25 += [0.0] * (n - len(bm25))
+        _, _, final, order = rerank_khop(
+            index, [rows], [bm25], [[c.get("retrieval_method") == "prf_bridge" for c in candidates]],
+            [[float(c.get("similarity_score", 0.0)) for c in candidates]], [[v[0] for v in cc]], [[v[1] for v in cc]],
+            [[int(c.get("hop_no", 1)) for c in candidates]], query_vecs=emb[:1], focus_vecs=emb[1:2] if q_focus else None,
+            hop_decay=w["hop_decay"], dense_weight=w["dense_weight"], bm25_weight=w["bm25_weight"],
+            focused_weight_hop2=w["focused_weight_hop2"], cov_weight=w["cov_weight"], cons_weight=w["cons_weight"],
+            rrf_lambda=w["rrf_lambda"])[0]
+        for c, f in zip(candidates, final):
+            c["final_score"] = float(f)
+        reranked = [candidates[int(i)] for i in order]
+        if not (suppress and enabled):
+            return reranked
+        kept = cluster_suppression(index, [[rows[int(i)] for i in order]], [[float(final[int(i)]) for i in order]],
+                                   cos_threshold=thr, keep_per_cluster=keep_m)[0]
+        return [reranked[int(k)] for k in kept]
 
     # -- incremental maintenance --------------------------------------------------------------------
     def add_notes(self, new_notes: List[Dict[str, Any]], rebuild_index: bool = False) -> bool:

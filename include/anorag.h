@@ -207,6 +207,59 @@ int anr_index_diversify(anr_index *h, int32_t device, int64_t nq, const int64_t 
  * kernels (or the upload of sim_host), [1] the decision kernel, [2] first copy in to last copy out. */
 int anr_diversify_timing(int32_t enable, float *ms3);
 
+/* The second hop of the multi-hop query path for a batch of nq queries, each with a ragged candidate list
+ * offs[q] .. offs[q + 1] of at most 1024 candidates (offs as in anr_index_diversify): the arithmetic of
+ * QueryProcessor._rerank_khop_candidates (query/query_processor.py:1549-1635) and _apply_cluster_suppression
+ * (:1637-1697), float64 in the reference's order of operations.  Host pointers in and out; any output pointer may be NULL.
+ *
+ * anr_index_khop_rerank.  Per candidate c: rows_host (row id of the index), bm25, is_prf (retrieval_method ==
+ * "prf_bridge") and prf_sim (its similarity_score), cov and cons (_compute_cov_cons), hop_no, and decay — the factor the
+ * caller prepared, hop_decay ** (hop_no - 1), or 1.0 where the reference does not multiply; the device only multiplies.
+ * Per query: query_host and focus_host, float32 [nq][dim] (focus_host may be NULL), and has_focus, uint8 [nq] (NULL: no
+ * query has a focus phrase).
+ *   dense[c]   = max(0.0, q . x_c / (||q|| ||x_c||)) from the stored float32 row, whatever the index's metric; 0.0 where
+ *                a norm is zero.  Products are exact in float64; lane l of a wave sums k = l, l + 64, ... in ascending k
+ *                and the 64 sums meet in a fixed butterfly, so the value depends on the two vectors alone.
+ *   focused[c] = the same with the focus vector; 0.0 for a query without a focus.
+ *   With dense_host != NULL, dense_host and focused_host (float64 [offs[nq]]; focused_host NULL = all 0.0) are taken as
+ *   given instead: h may then be NULL (the call runs on `device`) and rows_host and the vectors are ignored.
+ *   ranks (:1590-1601): 1-based positions by score descending, ties in candidate order — one ranking by dense, one by
+ *     bm25, and one by prf_sim over the candidates with is_prf only;
+ *   rrf = ((0.0 + 1.0 / (rrf_k + r_dense)) + 1.0 / (rrf_k + r_bm25)), and + 1.0 / (rrf_k + r_prf) last for a PRF candidate;
+ *   fw = focused_w2 when hop_no == 2, else max(0.0, focused_w2 - 0.10 * (hop_no - 2));
+ *   final = ((((dense_w * dense + bm25_w * bm25) + fw * focused) + cov_w * cov) + cons_w * cons) + rrf_lambda * rrf, then
+ *   final = final * decay[c];  order: the stable sort by final descending.
+ * Outputs: dense, focused, final_score float64 [offs[nq]]; order int32 [offs[nq]], query q's entries from offs[q],
+ * positions within the query's list, best first.
+ *
+ * anr_index_cluster_suppress.  cos(i, j) = G_ij / ((||x_i|| + 1e-8) (||x_j|| + 1e-8)), G the float64 Gram of the stored
+ * rows (the tile of anr_index_diversify, ||x_i|| = sqrt(G_ii)); with sim_host != NULL (concatenated C_q x C_q float64
+ * blocks, row-major; only j > i is read) the cosines are taken as given, h may be NULL and rows_host is ignored.  In input
+ * order i: an unused i forms a cluster with every later unused j with cos(i, j) >= thr (to the seed, not transitive); the
+ * cluster is stably sorted by score_host descending, its first keep_m are appended to the kept list, every member is marked
+ * used; at the end the kept list is stably sorted by score descending.  The input need not be sorted.
+ * Outputs: kept int32 [offs[nq]], query q's n_kept[q] entries from offs[q], positions within the query's list.
+ *
+ * ANR_EINVAL (nothing is written): a list longer than 1024, a row id outside [0, ntotal), keep_m < 1, a NaN in any score,
+ * weight or thr, offs not ascending from 0, h == NULL while rows must be read.  nq == 0 or all lists empty: ANR_OK. */
+typedef struct anr_khop_params {
+  double dense_w, bm25_w, focused_w2, cov_w, cons_w, rrf_lambda, rrf_k;
+} anr_khop_params;
+int anr_index_khop_rerank(anr_index *h, int32_t device, int64_t nq, const int64_t *offs, const int64_t *rows_host,
+                          const float *query_host, const float *focus_host, const uint8_t *has_focus,
+                          const double *dense_host, const double *focused_host, const double *bm25, const uint8_t *is_prf,
+                          const double *prf_sim, const double *cov, const int32_t *cons, const int32_t *hop_no,
+                          const double *decay, const anr_khop_params *p, double *dense, double *focused,
+                          double *final_score, int32_t *order);
+int anr_index_cluster_suppress(anr_index *h, int32_t device, int64_t nq, const int64_t *offs, const int64_t *rows_host,
+                               const double *sim_host, const double *score_host, double thr, int32_t keep_m, int32_t *kept,
+                               int32_t *n_kept);
+/* Developer timing of the two calls above (tools/khop_perf.py; process-wide, not for concurrent callers): enable != 0 makes
+ * later calls record HIP events; ms6 (may be NULL) receives the last timed calls' milliseconds: rerank [0] the dot kernel,
+ * [1] the rerank kernel, [2] first copy in to the last kernel; suppression [3] the Gram kernel (or the upload of sim_host),
+ * [4] the suppression kernel, [5] first copy in to the last kernel. */
+int anr_khop_timing(int32_t enable, float *ms6);
+
 /* Cluster quality of a labelling of the stored rows: the two measures of TopicClustering._analyze_clusters
  * (doc/clustering.py:171-215), which cluster_notes (:20-46) runs after every clustering.  L2 index without normalisation
  * only (ANR_EINVAL otherwise): the float32 rows are used exactly as stored.  Everything comes from one float64 Gram
